@@ -18,7 +18,12 @@ reports the fp32-exact 3-term variant (with its own `roofline`) and the plain-bf
 literal dtype; tolerance 3e-2, stated in the tests) beside it.  `config.convert_config4` = the conversion
 path (encode -> decode, configs[3]) on the GPU next to the CPU leg of `cpu_baseline`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR]
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step handed its caller to DIR as .npy files
+(float32; float64 from the CPU stand-in): `losses` {G, D_KL, logP}, `grads` (the flat gradient buffer), and the state the
+optimiser left, `params`, `adam_m`, `adam_v` (15 MB in all at any --frames).  Weights, batch and sampler seed are fixed,
+so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: bench.py launches its N ranks ITSELF
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`,
@@ -142,6 +147,8 @@ def parse(argv=None):
                    help='watchdog of everything after the headline measurement: when it expires rank 0 prints the line it has '
                         '(with "side_legs": "timed out ...") and every rank exits')
     p.add_argument('--master-port', type=int, default=0, help='rendezvous port of the self-launched ranks (0 = pick a free one)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the outputs of the last timed step to DIR/<name>.npy (see the module docstring)')
     p.add_argument('--standin', default=None,
                    help='TEST ONLY: python file providing make_engine(arch, args) -> CPU stand-in engine; the ranks then use '
                         'the gloo backend and only the launcher / process-group / timing logic of this file runs')
@@ -321,11 +328,23 @@ def load_standin(path):
     return mod
 
 
+def dump_outputs(path, st, eng):
+    """--dump-outputs: the losses, gradients, parameters and Adam slots after the last timed step, one .npy file each."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {'losses': st.mean_losses(), 'grads': st.grads, 'params': eng.params, 'adam_m': st.m, 'adam_v': st.v}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(self_launch(args, argv))
     import torch
@@ -426,6 +445,8 @@ def main(argv=None):
 
     F = args.frames
     dt, kern = timed(F, args.steps, args.warmup, None if (args.impl == 'auto' or standin) else args.timer_tag)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st, eng)      # before any side leg steps the model again
     frames_per_s = world * F * args.steps / dt
     steps_per_s = args.steps / dt
     out = {

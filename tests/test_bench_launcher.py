@@ -60,3 +60,25 @@ def test_refuses_without_enough_devices():
     r = run(['--gpus', '2', '--steps', '1', '--warmup', '0'])
     assert r.returncode != 0 and 'refusing' in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith('{')]
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the last timed step's losses, gradients and optimiser state; the same arguments give the same
+    arrays, and the number of timed steps is what --steps says (one more step moves the parameters)."""
+    import numpy as np
+    names = ('losses', 'grads', 'params', 'adam_m', 'adam_v')
+
+    def dump(tag, steps):
+        d = tmp_path / tag
+        r = run(['--steps', str(steps), '--warmup', '1', '--frames', '4', '--standin', STANDIN, '--dump-outputs', str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert last_json(r.stdout)['steps'] == steps
+        return {n: np.load(str(d / (n + '.npy'))) for n in names}
+
+    a, b, c = dump('a', 2), dump('b', 2), dump('c', 3)
+    assert a['losses'].shape == (3,) and np.all(np.isfinite(a['losses']))
+    assert a['grads'].shape == a['params'].shape == a['adam_m'].shape == a['adam_v'].shape
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[n], b[n]), n
+    assert not np.array_equal(a['params'], c['params'])
