@@ -275,6 +275,22 @@ int vaenpvc_tanhize_fwd(const float* d_sp, const float* d_xmin, const float* d_x
 int vaenpvc_tanhize_bwd(const float* d_x, const float* d_xmin, const float* d_xmax, float* d_sp,
                         int64_t F, int32_t H, void* stream);
 
+/* Global-variance (GV) post-filter fused with Tanhize.backward_process (not in the reference: README.md "TODO: GV",
+ * and "Global variance post-filtering was not included in this repo").  d_x [F,H] is decoder output in the Tanhize
+ * domain holding n_seg utterances back to back: utterance u is rows d_offsets[u] .. d_offsets[u+1] (device int64
+ * [n_seg+1], non-decreasing, [0] = 0, [n_seg] = F; NOT checked here -- the binding checks it on the host).  Per
+ * utterance and bin, with c = (x*.5+.5)*(xmax-xmin)+xmin, mu_c / v_c its utterance mean / biased variance and
+ * g = d_gv[bin] (the target speaker's mean utterance variance, etc/<spk>_gv.npf):
+ *     d_sp = mu_c + sqrt(g / v_c) * (c - mu_c)   where v_c > 1e-8,
+ *     d_sp = vaenpvc_tanhize_bwd's bytes           elsewhere (1-frame utterance, constant bin, xmax == xmin).
+ * An utterance's output depends only on its own frames (bit for bit, whatever its offset or neighbours in the batch).
+ * d_sp must not overlap d_x.  d_ws: >= vaenpvc_gv_workspace_bytes(F, n_seg, H) bytes, 16-byte aligned
+ * (VAENPVC_E_WORKSPACE if shorter or NULL).  F >= 0, n_seg >= 1, H >= 1; F is not limited to 2^18 here. */
+int64_t vaenpvc_gv_workspace_bytes(int64_t F, int32_t n_seg, int32_t H);
+int vaenpvc_gv_postfilter(const float* d_x, const int64_t* d_offsets, int32_t n_seg, int64_t F, int32_t H,
+                          const float* d_xmin, const float* d_xmax, const float* d_gv, float* d_sp,
+                          void* d_ws, size_t ws_bytes, void* stream);
+
 /* analyzer.read record slicing (analyzer.py:113-127): rows of `rec_floats` float32
  * (1029) -> x = Tanhize(row[0:H]) and y = int64(row[rec_floats-1]) (bit-exact cast). */
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H,

@@ -4,9 +4,10 @@
         --checkpoint logdir/train/<stamp>/model.ckpt-<N>
 
 Device path per utterance (convert.py:79-89): Tanhize -> encode (z_mu) -> decode with the
-target speaker id -> inverse Tanhize.  The log-F0 transform (convert.py:51-57) runs on the
-host.  WORLD synthesis needs pyworld (absent here): when it is importable a wav is written,
-otherwise the converted features are saved as `<src>-<trg>-<basename>.npz`.
+target speaker id -> inverse Tanhize (with `--gv`: the global-variance post-filter fused with
+it).  The log-F0 transform (convert.py:51-57) runs on the host.  WORLD synthesis needs pyworld
+(absent here): when it is importable a wav is written, otherwise the converted features are
+saved as `<src>-<trg>-<basename>.npz`.
 """
 import argparse
 import glob
@@ -38,6 +39,10 @@ def parse_args(argv=None):
                         'utterance of <= 512 frames then runs on the fp32-exact whole-frame kernels and its output does not '
                         'depend on its neighbours in the glob order.  The default gathers files onto the large-batch kernels '
                         '(2-term bf16 operands: within the 1e-4 relative parity bar, not bit-reproducible per file)')
+    p.add_argument('--gv', action='store_true',
+                   help='(not in the reference) global-variance post-filter: every bin of a converted utterance keeps its '
+                        'mean and takes the target speaker\'s mean utterance variance, ./etc/<trg>_gv.npf (written by '
+                        'build.py).  Off by default: the output is then the unfiltered conversion')
     args = p.parse_args(argv)
     if args.model is None:                                               # convert.py:23-27
         raise ValueError('\n  You MUST specify `model`.'
@@ -69,8 +74,22 @@ def convert_f0(f0, src, trg, etc_dir='./etc'):
     return lf0
 
 
-def convert_utterance(machine, normalizer, sp, trg_id):
-    """The device tensor path of convert.py:79-89 for one utterance: sp [N,513] -> converted sp."""
+def load_gv(trg, H, etc_dir='./etc'):
+    """The target speaker's global variance (build.py: `<spk>_gv.npf`, H float32), checked before any device work."""
+    from analyzer import load_npf
+    path = os.path.join(etc_dir, '{}_gv.npf'.format(trg))
+    if not os.path.isfile(path):
+        raise FileNotFoundError('%s: no global-variance statistics for speaker %s (written by build.py)' % (path, trg))
+    gv = load_npf(path, count=H)
+    if not np.all(np.isfinite(gv)) or np.any(gv < 0):
+        raise ValueError('%s: global variances must be finite and >= 0' % path)
+    return gv
+
+
+def convert_utterance(machine, normalizer, sp, trg_id, gv=None, lengths=None):
+    """The device tensor path of convert.py:79-89 for one utterance: sp [N,513] -> converted sp.  gv (target speaker's
+    global variance, [513]): the GV post-filter replaces the inverse Tanhize; `lengths` then splits the rows into
+    utterances stored back to back (default: one utterance)."""
     import torch
     x = normalizer.forward_process(sp)                                    # [N,513] in [-1,1]
     x = x.view(x.shape[0], 1, x.shape[1], 1)                              # nh_to_nchw (convert.py:60-63)
@@ -78,23 +97,29 @@ def convert_utterance(machine, normalizer, sp, trg_id):
     z = machine.encode(x)
     x_t = machine.decode(z, y_t)                                          # NHWC [N,513,1,1]
     x_t = x_t.reshape(x_t.shape[0], -1)                                   # tf.squeeze
-    return normalizer.backward_process(x_t)
+    if gv is None:
+        return normalizer.backward_process(x_t)
+    gv = torch.as_tensor(gv, dtype=torch.float32).to(x_t.device)
+    return machine.engine.gv_postfilter(x_t, [x_t.shape[0]] if lengths is None else lengths, normalizer.xmin,
+                                        normalizer.xmax, gv)
 
 
-def convert_utterances(machine, normalizer, sps, trg_id):
+def convert_utterances(machine, normalizer, sps, trg_id, gv=None):
     """The same tensor path for SEVERAL utterances in one launch.  The model is frame-wise (W = 1: every frame is an independent
     sample of the network, model/vae.py:72-103), so the frames of consecutive files can share one encode -> decode call and the
     result is cut back at the file boundaries.  One utterance is a few hundred to ~2 000 frames, a size at which a launch
     sequence is latency-bound (0.4 ms for 1 024 frames against 2.5 ms for 32 768); the reference runs one sess.run per file
-    (convert.py:105-116).  Returns the converted sp of every utterance, in order."""
+    (convert.py:105-116).  With `gv` the post-filter takes its statistics per file (one call for the group).  Returns the
+    converted sp of every utterance, in order."""
     import torch
     sps = [np.ascontiguousarray(sp, np.float32) for sp in sps]
     if not sps:
         return []
     if len(sps) == 1:
-        return [convert_utterance(machine, normalizer, sps[0], trg_id)]
-    out = convert_utterance(machine, normalizer, np.concatenate(sps, axis=0), trg_id)
-    return list(torch.split(out, [sp.shape[0] for sp in sps], dim=0))
+        return [convert_utterance(machine, normalizer, sps[0], trg_id, gv=gv)]
+    lengths = [sp.shape[0] for sp in sps]
+    out = convert_utterance(machine, normalizer, np.concatenate(sps, axis=0), trg_id, gv=gv, lengths=lengths)
+    return list(torch.split(out, lengths, dim=0))
 
 
 def batched(features, batch_frames):
@@ -122,7 +147,13 @@ def main(argv=None):
     arch_file = glob.glob(os.path.join(logdir, 'architecture*.json'))[0]  # should only be 1 file
     with open(arch_file) as fp:
         arch = json.load(fp)
+    gv = None
+    if args.gv:
+        gv = load_gv(args.trg, int(arch['hwc'][0]))
     normalizer = Tanhize(xmax=load_npf('./etc/xmax.npf'), xmin=load_npf('./etc/xmin.npf'))
+    if gv is not None:
+        import torch
+        gv = torch.as_tensor(gv).to(normalizer.xmin.device)                # once: no host-to-device copy per group
     machine = MODEL(arch)
     load(machine.engine, logdir, ckpt=ckpt)
     output_dir = get_default_output(args.output_dir)
@@ -137,7 +168,7 @@ def main(argv=None):
     from analyzer import pw2wav
     machine.engine.validate_ids(_ids(machine, 1, trg_id))
     for group in batched(read_whole_features(args.file_pattern.format(args.src)), args.batch_frames):
-        converted = convert_utterances(machine, normalizer, [feat['sp'] for feat in group], trg_id)
+        converted = convert_utterances(machine, normalizer, [feat['sp'] for feat in group], trg_id, gv=gv)
         for feat, sp_t in zip(group, converted):
             sp = sp_t.cpu().numpy()
             f0 = convert_f0(feat['f0'], args.src, args.trg)

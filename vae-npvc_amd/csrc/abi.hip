@@ -1,4 +1,5 @@
 // abi.hip -- the extern "C" surface declared in include/vaenpvc.h (+ the developer hooks of include/vaenpvc_debug.h).
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -171,7 +172,7 @@ int vaenpvc_timer_read(vaenpvc_ctx* ctx, double* total_ms, int64_t* launches) {
   return 0;
 }
 
-int vaenpvc_abi_version(void) { return 3; }
+int vaenpvc_abi_version(void) { return 4; }
 const char* vaenpvc_last_error(void) { return g_err; }
 
 int vaenpvc_ctx_create(const vaenpvc_arch* arch, vaenpvc_ctx** out) {
@@ -468,6 +469,34 @@ int vaenpvc_tanhize_bwd(const float* d_x, const float* d_xmin, const float* d_xm
   if (!d_x || !d_xmin || !d_xmax || !d_sp || F < 1 || H < 1) return fail(VAENPVC_E_ARG, "bad argument");
   launch_tanhize(d_x, d_xmin, d_xmax, d_sp, F, H, false, (hipStream_t)stream);
   return check_launch("tanhize_bwd");
+}
+
+static bool gv_shape_ok(int64_t F, int32_t n_seg, int32_t H) {
+  // launch grids fit 32 bits; byte counts of x and of the workspace fit int64 with room
+  return F >= 0 && n_seg > 0 && H > 0 && F <= (1LL << 56) / H && gv_chunk_grid(F, n_seg) <= INT32_MAX &&
+         gv_chunk_grid(F, n_seg) * H <= (1LL << 56) && H <= (1 << 23) &&
+         (int64_t)n_seg * ((H + 31) / 32) <= INT32_MAX;
+}
+
+int64_t vaenpvc_gv_workspace_bytes(int64_t F, int32_t n_seg, int32_t H) {
+  if (!gv_shape_ok(F, n_seg, H)) return fail(VAENPVC_E_ARG, "bad argument (F %lld, n_seg %d, H %d)", (long long)F, n_seg, H);
+  return gv_workspace_bytes(F, n_seg, H);
+}
+
+int vaenpvc_gv_postfilter(const float* d_x, const int64_t* d_offsets, int32_t n_seg, int64_t F, int32_t H,
+                          const float* d_xmin, const float* d_xmax, const float* d_gv, float* d_sp, void* d_ws,
+                          size_t ws_bytes, void* stream) {
+  if (!d_x || !d_offsets || !d_xmin || !d_xmax || !d_gv || !d_sp) return fail(VAENPVC_E_ARG, "null argument");
+  if (!gv_shape_ok(F, n_seg, H)) return fail(VAENPVC_E_ARG, "bad argument (F %lld, n_seg %d, H %d)", (long long)F, n_seg, H);
+  const char *x0 = (const char*)d_x, *s0 = (const char*)d_sp;
+  const int64_t nbytes = F * (int64_t)H * 4;
+  if (nbytes > 0 && x0 < s0 + nbytes && s0 < x0 + nbytes) return fail(VAENPVC_E_ARG, "d_sp must not overlap d_x");
+  const int64_t need = gv_workspace_bytes(F, n_seg, H);
+  if (d_ws == nullptr || ws_bytes < (size_t)need)
+    return fail(VAENPVC_E_WORKSPACE, "workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+  if (((uintptr_t)d_ws & 15) != 0) return fail(VAENPVC_E_ARG, "workspace must be 16-byte aligned");
+  launch_gv_postfilter(d_x, d_offsets, n_seg, F, H, d_xmin, d_xmax, d_gv, d_sp, d_ws, (hipStream_t)stream);
+  return check_launch("gv_postfilter");
 }
 
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H, const float* d_xmin,

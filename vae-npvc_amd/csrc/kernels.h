@@ -96,6 +96,13 @@ void launch_philox_uniform(float* out, int64_t n, PhiloxKey key, hipStream_t s);
 void launch_summary(const float* d, int64_t n, const float* edges, int n_edges, double* stats, unsigned long long* counts,
                     hipStream_t s);
 
+// ---- global-variance post-filter of the conversion path (gfx950_gv.hip) ----------
+// workgroups of the per-chunk launches, and workspace bytes: (x0, mean, M2) per chunk and bin + the per-bin map per utterance
+int64_t gv_chunk_grid(int64_t F, int n_seg);
+int64_t gv_workspace_bytes(int64_t F, int n_seg, int H);
+void launch_gv_postfilter(const float* x, const int64_t* off, int n_seg, int64_t F, int H, const float* xmin,
+                          const float* xmax, const float* gv, float* out, void* ws, hipStream_t s);
+
 // ---- tuned gfx950 kernels for the VCC2016 geometry (gfx950_*.hip) ----------------
 namespace tuned {
 // step masks: bit set = use the tuned kernel for that step, clear = generic kernel.

@@ -90,6 +90,7 @@ class Engine(object):
         self.z_dim, self.H = self._astruct.z_dim, self._astruct.H
         self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         self._ws = None
+        self._gv_ws = None          # workspace of gv_postfilter (separate: its size follows the batch, not the model)
         self._loss3 = torch.zeros(3, dtype=torch.float32, device=self.device)
         self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._bucket_cb = None      # keeps the ctypes thunk alive while it is registered
@@ -365,6 +366,38 @@ class Engine(object):
         with self._on_device():
             L.check(fn(sp.data_ptr(), xmin.data_ptr(), xmax.data_ptr(), out.data_ptr(), sp.shape[0], sp.shape[1],
                        self._stream()), 'tanhize')
+        return out
+
+    def gv_postfilter(self, x, lengths, xmin, xmax, gv):
+        """Global-variance post-filter fused with the inverse Tanhize (vaenpvc_gv_postfilter): x float32 CUDA [F, H] in
+        the Tanhize domain, holding utterances of `lengths` frames (host ints, sum F) back to back; xmin / xmax / gv
+        float32 CUDA [H].  Returns the filtered sp [F, H] (a new tensor), enqueued on the current stream."""
+        if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2:
+            raise TypeError('x must be a float32 CUDA [F, H] tensor')
+        x = x.contiguous()
+        F, H = x.shape
+        for name, t in (('xmin', xmin), ('xmax', xmax), ('gv', gv)):
+            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != H:
+                raise TypeError('%s must be a float32 CUDA tensor of %d values' % (name, H))
+        lengths = [int(n) for n in lengths]
+        if not lengths or min(lengths) < 0 or sum(lengths) != F:
+            raise ValueError('lengths must be >= 0 and add up to the %d frames of x (got %s)' % (F, lengths))
+        if F == 0:
+            return torch.empty_like(x)
+        offsets = torch.tensor([0] + lengths, dtype=torch.int64).cumsum(0)
+        offsets = offsets.pin_memory().to(self.device, non_blocking=True)
+        need = int(self.lib.vaenpvc_gv_workspace_bytes(F, len(lengths), H))
+        if need < 0:
+            L.check(need, 'gv_workspace_bytes')
+        if self._gv_ws is None or self._gv_ws.numel() < need:
+            self._gv_ws = None
+            self._gv_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = torch.empty_like(x)
+        with self._on_device():
+            L.check(self.lib.vaenpvc_gv_postfilter(x.data_ptr(), offsets.data_ptr(), len(lengths), F, H,
+                                                   xmin.contiguous().data_ptr(), xmax.contiguous().data_ptr(),
+                                                   gv.contiguous().data_ptr(), out.data_ptr(), self._gv_ws.data_ptr(),
+                                                   need, self._stream()), 'gv_postfilter')
         return out
 
     def unpack_records(self, rec, xmin, xmax, index=None):

@@ -8,7 +8,7 @@ CSRC = os.path.normpath(os.path.join(_HERE, '..', 'csrc'))
 # VAENPVC_LIB: developer override used by scripts/build_variant.sh (kernel experiments)
 LIB_PATH = os.environ.get('VAENPVC_LIB') or os.path.join(CSRC, 'libvaenpvc_hip.so')
 MAX_LAYERS = 8
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 MODE_INFER, MODE_TRAIN = 0, 1
 IMPL_AUTO, IMPL_GENERIC = 0, 1
@@ -70,6 +70,8 @@ SIGNATURES = {
     'vaenpvc_set_tuned_masks': (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     'vaenpvc_timer_select': (C.c_int, [_P, C.c_char_p]),
     'vaenpvc_timer_read': (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(_I64)]),
+    'vaenpvc_gv_workspace_bytes': (_I64, [_I64, _I32, _I32]),
+    'vaenpvc_gv_postfilter': (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     'vaenpvc_unpack_records': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_gather_unpack_records': (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_set_precision': (C.c_int, [_P, C.c_int]),
