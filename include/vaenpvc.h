@@ -291,6 +291,28 @@ int vaenpvc_gv_postfilter(const float* d_x, const int64_t* d_offsets, int32_t n_
                           const float* d_xmin, const float* d_xmax, const float* d_gv, float* d_sp,
                           void* d_ws, size_t ws_bytes, void* stream);
 
+/* WORLD-style waveform synthesis (the reference's convert.py:105-114 -> analyzer.py:pw2wav -> pyworld.synthesize; pyworld
+ * is a CPU C library this project does not have).  The algorithm is DESIGN.md section 14: WORLD's Synthesis() structure
+ * (pulses from a float64 phase scan, minimum-phase periodic and aperiodic responses from 1024-point FFTs, overlap-add)
+ * with documented deviations; sample-level equality with pyworld is not claimed.  n_seg utterances back to back:
+ * utterance u is frames d_frame_offsets[u] .. [u+1] of d_f0 [F], d_sp [F,H] (log10, energy-normalised as in the .bin
+ * files), d_en [F], d_ap [F,H], and samples d_sample_offsets[u] .. [u+1] of d_y [S] (float32), with
+ * S_u = floor(T_u * frame_period_ms * fs / 1000) computed in float64 (pyworld's y_length).  Both offset arrays are device
+ * int64 [n_seg+1], non-decreasing, [0] = 0, [n_seg] = F resp. S, every T_u >= 1; NOT checked here -- the binding checks
+ * them on the host (a malformed array cannot make a kernel write outside d_y or d_ws).  The noise is the Philox draw of
+ * vaenpvc_philox_normal (key `seed`, offset 0), element index counted from the utterance's first pulse.  Per-sample f0 is
+ * capped at VAENPVC_SYNTH_F0_CEIL Hz, which bounds the pulses per utterance by floor(S_u * 1000 / fs) + 1; a pulse beyond
+ * it is dropped.  An utterance's output depends only on its own frames and `seed` (bit for bit, whatever its offset or
+ * neighbours in the batch).  H must be 513 (FFT size 1024), 8000 <= fs <= 48000, frame_period_ms finite and > 0; d_y must
+ * not overlap an input.  d_ws: >= vaenpvc_synth_workspace_bytes(n_seg, S, H, fs) bytes, 16-byte aligned
+ * (VAENPVC_E_WORKSPACE if shorter or NULL): about 4 KiB per pulse slot, (floor(S * 1000 / fs) + n_seg) slots. */
+#define VAENPVC_SYNTH_F0_CEIL 1000
+int64_t vaenpvc_synth_workspace_bytes(int32_t n_seg, int64_t S, int32_t H, int32_t fs);
+int vaenpvc_synthesize(const float* d_f0, const float* d_sp, const float* d_en, const float* d_ap,
+                       const int64_t* d_frame_offsets, const int64_t* d_sample_offsets, int32_t n_seg, int64_t F,
+                       int64_t S, int32_t H, int32_t fs, double frame_period_ms, uint64_t seed, float* d_y, void* d_ws,
+                       size_t ws_bytes, void* stream);
+
 /* analyzer.read record slicing (analyzer.py:113-127): rows of `rec_floats` float32
  * (1029) -> x = Tanhize(row[0:H]) and y = int64(row[rec_floats-1]) (bit-exact cast). */
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H,

@@ -5,15 +5,17 @@
 
 Device path per utterance (convert.py:79-89): Tanhize -> encode (z_mu) -> decode with the
 target speaker id -> inverse Tanhize (with `--gv`: the global-variance post-filter fused with
-it).  The log-F0 transform (convert.py:51-57) runs on the host.  WORLD synthesis needs pyworld
-(absent here): when it is importable a wav is written, otherwise the converted features are
-saved as `<src>-<trg>-<basename>.npz`.
+it).  The log-F0 transform (convert.py:51-57) runs on the host.  `--vocoder pyworld` (the default)
+synthesises with pyworld when it is importable and writes a wav, otherwise it saves the converted
+features as `<src>-<trg>-<basename>.npz`.  `--vocoder device` synthesises every group of utterances
+on the GPU (Engine.synthesize) and writes 16-bit PCM wavs.
 """
 import argparse
 import glob
 import json
 import os
 import sys
+import wave
 from datetime import datetime
 from importlib import import_module
 
@@ -22,6 +24,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 FS = 16000
+FRAME_PERIOD = 5.0          # ms: pyworld's default, used by the reference's analysis and synthesis
 
 
 def parse_args(argv=None):
@@ -43,6 +46,10 @@ def parse_args(argv=None):
                    help='(not in the reference) global-variance post-filter: every bin of a converted utterance keeps its '
                         'mean and takes the target speaker\'s mean utterance variance, ./etc/<trg>_gv.npf (written by '
                         'build.py).  Off by default: the output is then the unfiltered conversion')
+    p.add_argument('--vocoder', choices=['pyworld', 'device'], default='pyworld',
+                   help='(not in the reference) pyworld (default, the reference\'s path): a wav through pyworld when it '
+                        'imports, otherwise the converted features as .npz; device: WORLD-style synthesis on the GPU, one '
+                        'call per group of utterances, 16-bit PCM wavs (no pyworld / soundfile import)')
     args = p.parse_args(argv)
     if args.model is None:                                               # convert.py:23-27
         raise ValueError('\n  You MUST specify `model`.'
@@ -122,6 +129,33 @@ def convert_utterances(machine, normalizer, sps, trg_id, gv=None):
     return list(torch.split(out, lengths, dim=0))
 
 
+def write_wav(path, y, fs=FS):
+    """Mono 16-bit PCM through the standard library: rint(clip(y, -1, 1) * 32767)."""
+    pcm = np.rint(np.clip(np.asarray(y, np.float64), -1.0, 1.0) * 32767.0).astype('<i2')
+    with wave.open(path, 'wb') as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(fs))
+        w.writeframes(pcm.tobytes())
+
+
+def synthesize_group(machine, group, converted, src, trg, etc_dir='./etc'):
+    """Device vocoder for one group of utterances: the converted sp stays on the device, the converted f0, en and ap are
+    uploaded, one Engine.synthesize call.  Returns the waveforms (host float32), one per utterance."""
+    import torch
+    dev = machine.engine.device
+    lengths = [int(feat['sp'].shape[0]) for feat in group]
+    sp = converted[0] if len(converted) == 1 else torch.cat(converted, dim=0)
+    f0 = np.concatenate([convert_f0(feat['f0'], src, trg, etc_dir) for feat in group])
+    en = np.concatenate([np.asarray(feat['en'], np.float32) for feat in group])
+    ap = np.concatenate([np.asarray(feat['ap'], np.float32) for feat in group])
+    up = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (f0, en, ap)]
+    y, samples = machine.engine.synthesize(up[0], sp.contiguous(), up[1], up[2], lengths, fs=FS,
+                                           frame_period=FRAME_PERIOD)
+    y = y.cpu().numpy()
+    return np.split(y, np.cumsum(samples)[:-1])
+
+
 def batched(features, batch_frames):
     """Groups the utterance stream: consecutive feature dicts whose frame counts add up to at most `batch_frames` (an utterance
     longer than that goes alone; batch_frames <= 0: every utterance alone).  Order is preserved."""
@@ -159,6 +193,13 @@ def main(argv=None):
     output_dir = get_default_output(args.output_dir)
     os.makedirs(output_dir, exist_ok=True)
     trg_id = SPEAKERS.index(args.trg)
+    machine.engine.validate_ids(_ids(machine, 1, trg_id))
+    if args.vocoder == 'device':
+        for group in batched(read_whole_features(args.file_pattern.format(args.src)), args.batch_frames):
+            converted = convert_utterances(machine, normalizer, [feat['sp'] for feat in group], trg_id, gv=gv)
+            for feat, y in zip(group, synthesize_group(machine, group, converted, args.src, args.trg)):
+                write_wav(make_output_name(output_dir, feat['filename'], args.src, args.trg, 'wav'), y, FS)
+        return output_dir
     try:
         import pyworld  # noqa: F401  (absent in this image: the features are saved instead of a wav)
         import soundfile as sf
@@ -166,7 +207,6 @@ def main(argv=None):
     except ImportError:
         sf, have_world = None, False
     from analyzer import pw2wav
-    machine.engine.validate_ids(_ids(machine, 1, trg_id))
     for group in batched(read_whole_features(args.file_pattern.format(args.src)), args.batch_frames):
         converted = convert_utterances(machine, normalizer, [feat['sp'] for feat in group], trg_id, gv=gv)
         for feat, sp_t in zip(group, converted):

@@ -499,6 +499,47 @@ int vaenpvc_gv_postfilter(const float* d_x, const int64_t* d_offsets, int32_t n_
   return check_launch("gv_postfilter");
 }
 
+static bool synth_shape_ok(int32_t n_seg, int64_t S, int32_t H, int32_t fs) {
+  // pulse samples and slot counts fit int32, launch grids 32 bits
+  return n_seg > 0 && n_seg < (1 << 24) && S >= 0 && S <= INT32_MAX && H == 513 && fs >= 8000 && fs <= 48000;
+}
+
+int64_t vaenpvc_synth_workspace_bytes(int32_t n_seg, int64_t S, int32_t H, int32_t fs) {
+  if (!synth_shape_ok(n_seg, S, H, fs))
+    return fail(VAENPVC_E_ARG, "bad argument (n_seg %d, S %lld, H %d, fs %d)", n_seg, (long long)S, H, fs);
+  return synth_workspace_bytes(n_seg, S, fs);
+}
+
+static bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+  const char *x = (const char*)a, *y = (const char*)b;
+  return na > 0 && nb > 0 && x < y + nb && y < x + na;
+}
+
+int vaenpvc_synthesize(const float* d_f0, const float* d_sp, const float* d_en, const float* d_ap,
+                       const int64_t* d_frame_offsets, const int64_t* d_sample_offsets, int32_t n_seg, int64_t F,
+                       int64_t S, int32_t H, int32_t fs, double frame_period_ms, uint64_t seed, float* d_y, void* d_ws,
+                       size_t ws_bytes, void* stream) {
+  if (!d_f0 || !d_sp || !d_en || !d_ap || !d_frame_offsets || !d_sample_offsets || !d_y)
+    return fail(VAENPVC_E_ARG, "null argument");
+  if (!synth_shape_ok(n_seg, S, H, fs) || F < n_seg || F > INT32_MAX)
+    return fail(VAENPVC_E_ARG, "bad argument (n_seg %d, F %lld, S %lld, H %d, fs %d)", n_seg, (long long)F,
+                (long long)S, H, fs);
+  if (!std::isfinite(frame_period_ms) || !(frame_period_ms > 0.0))
+    return fail(VAENPVC_E_ARG, "frame period must be finite and > 0 (got %g ms)", frame_period_ms);
+  const int64_t ny = S * 4, nf = F * 4, nfh = F * (int64_t)H * 4, no = ((int64_t)n_seg + 1) * 8;
+  if (overlaps(d_y, ny, d_f0, nf) || overlaps(d_y, ny, d_sp, nfh) || overlaps(d_y, ny, d_en, nf) ||
+      overlaps(d_y, ny, d_ap, nfh) || overlaps(d_y, ny, d_frame_offsets, no) || overlaps(d_y, ny, d_sample_offsets, no))
+    return fail(VAENPVC_E_ARG, "d_y must not overlap an input");
+  const int64_t need = synth_workspace_bytes(n_seg, S, fs);
+  if (d_ws == nullptr || ws_bytes < (size_t)need)
+    return fail(VAENPVC_E_WORKSPACE, "workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+  if (((uintptr_t)d_ws & 15) != 0) return fail(VAENPVC_E_ARG, "workspace must be 16-byte aligned");
+  if (overlaps(d_y, ny, d_ws, need)) return fail(VAENPVC_E_ARG, "d_y must not overlap the workspace");
+  launch_synthesize(d_f0, d_sp, d_en, d_ap, d_frame_offsets, d_sample_offsets, n_seg, F, S, fs, frame_period_ms, seed,
+                    d_y, d_ws, (hipStream_t)stream);
+  return check_launch("synthesize");
+}
+
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H, const float* d_xmin,
                            const float* d_xmax, float* d_x, int64_t* d_y, void* stream) {
   if (!d_records || !d_xmin || !d_xmax || !d_x || !d_y || F < 1 || H < 1 || rec_floats < H + 1)

@@ -103,6 +103,15 @@ int64_t gv_workspace_bytes(int64_t F, int n_seg, int H);
 void launch_gv_postfilter(const float* x, const int64_t* off, int n_seg, int64_t F, int H, const float* xmin,
                           const float* xmax, const float* gv, float* out, void* ws, hipStream_t s);
 
+// ---- WORLD-style synthesis of the conversion path (gfx950_synth.hip) -------------
+// pulse slots (floor(S*1000/fs) + n_seg) and workspace bytes: counts, their prefix, per slot (sample, shift + voicing,
+// 4 KiB segment)
+int64_t synth_slots(int n_seg, int64_t S, int fs);
+int64_t synth_workspace_bytes(int n_seg, int64_t S, int fs);
+void launch_synthesize(const float* f0, const float* sp, const float* en, const float* ap, const int64_t* foff,
+                       const int64_t* soff, int n_seg, int64_t F, int64_t S, int fs, double frame_period_ms,
+                       uint64_t seed, float* y, void* ws, hipStream_t s);
+
 // ---- tuned gfx950 kernels for the VCC2016 geometry (gfx950_*.hip) ----------------
 namespace tuned {
 // step masks: bit set = use the tuned kernel for that step, clear = generic kernel.

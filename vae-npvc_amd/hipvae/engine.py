@@ -91,6 +91,7 @@ class Engine(object):
         self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         self._ws = None
         self._gv_ws = None          # workspace of gv_postfilter (separate: its size follows the batch, not the model)
+        self._synth_ws = None       # workspace of synthesize (likewise)
         self._loss3 = torch.zeros(3, dtype=torch.float32, device=self.device)
         self._flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._bucket_cb = None      # keeps the ctypes thunk alive while it is registered
@@ -399,6 +400,44 @@ class Engine(object):
                                                    gv.contiguous().data_ptr(), out.data_ptr(), self._gv_ws.data_ptr(),
                                                    need, self._stream()), 'gv_postfilter')
         return out
+
+    def synthesize(self, f0, sp, en, ap, lengths, fs=16000, frame_period=5.0, seed=0):
+        """WORLD-style synthesis (vaenpvc_synthesize) of utterances of `lengths` frames (host ints,
+        each >= 1) stored back to back: f0 / en float32 CUDA [F], sp (log10, energy-normalised) / ap float32 CUDA
+        [F, 513].  Returns (y, samples): the float32 CUDA waveforms back to back and the per-utterance sample counts
+        floor(T * frame_period * fs / 1000), enqueued on the current stream."""
+        lengths = [int(n) for n in lengths]
+        if not lengths or min(lengths) < 1:
+            raise ValueError('lengths must be a non-empty list of frame counts >= 1 (got %s)' % (lengths,))
+        F = sum(lengths)
+        for name, t, shape in (('f0', f0, (F,)), ('sp', sp, (F, 513)), ('en', en, (F,)), ('ap', ap, (F, 513))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
+                raise TypeError('%s must be a float32 CUDA tensor of shape %s' % (name, shape))
+        fs, frame_period = int(fs), float(frame_period)
+        if not 8000 <= fs <= 48000:
+            raise ValueError('fs must be in [8000, 48000] (got %d)' % fs)
+        if not math.isfinite(frame_period) or frame_period <= 0:
+            raise ValueError('frame_period must be finite and > 0 (got %r)' % frame_period)
+        samples = [int(math.floor(T * frame_period * fs / 1000.0)) for T in lengths]
+        S = sum(samples)
+        y = torch.empty(S, dtype=torch.float32, device=self.device)
+        if S == 0:
+            return y, samples
+        f0, sp, en, ap = (t.contiguous() for t in (f0, sp, en, ap))
+        offs = torch.tensor([[0] + lengths, [0] + samples], dtype=torch.int64).cumsum(1)
+        offs = offs.pin_memory().to(self.device, non_blocking=True)
+        need = int(self.lib.vaenpvc_synth_workspace_bytes(len(lengths), S, 513, fs))
+        if need < 0:
+            L.check(need, 'synth_workspace_bytes')
+        if self._synth_ws is None or self._synth_ws.numel() < need:
+            self._synth_ws = None
+            self._synth_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with self._on_device():
+            L.check(self.lib.vaenpvc_synthesize(f0.data_ptr(), sp.data_ptr(), en.data_ptr(), ap.data_ptr(),
+                                                offs[0].data_ptr(), offs[1].data_ptr(), len(lengths), F, S, 513, fs,
+                                                frame_period, int(seed) & (2 ** 64 - 1), y.data_ptr(),
+                                                self._synth_ws.data_ptr(), need, self._stream()), 'synthesize')
+        return y, samples
 
     def unpack_records(self, rec, xmin, xmax, index=None):
         """x = Tanhize(rec[i, :H]), y = int64(rec[i, -1]) for i in `index` (int64 CUDA tensor; default: all rows).
