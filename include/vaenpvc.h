@@ -313,6 +313,44 @@ int vaenpvc_synthesize(const float* d_f0, const float* d_sp, const float* d_en, 
                        int64_t S, int32_t H, int32_t fs, double frame_period_ms, uint64_t seed, float* d_y, void* d_ws,
                        size_t ws_bytes, void* stream);
 
+/* WORLD-style feature analysis (the reference's analyzer.py:25-47: librosa.load -> pyworld dio(f0_ceil = --f0_ceil) ->
+ * stonemask -> cheaptrick(fft_size 1024) -> d4c, then en = sum(sp + 1e-10), sp = log10(sp / en); pyworld is a CPU C
+ * library this project does not have).  The algorithm is DESIGN.md section 15 (DIO with 2 channels per octave, speed 1,
+ * allowed range 0.1; StoneMask; CheapTrick q1 = -0.15; D4C threshold 0.85), restated by tests/world_analysis_ref.py;
+ * sample-level equality with pyworld is not claimed.  n_seg utterances back to back: utterance u is samples
+ * d_sample_offsets[u] .. [u+1] of d_x [S] (float32, librosa's int16 / 32768 scale) and frames d_frame_offsets[u] .. [u+1]
+ * of the outputs, with T_u = (int)(1000 S_u / fs / frame_period_ms) + 1 computed in float64 (GetSamplesForDIO); frame i
+ * is at i * frame_period_ms / 1000 s.  Both offset arrays are device int64 [n_seg+1], non-decreasing, [0] = 0,
+ * [n_seg] = S resp. F, every S_u >= 1; NOT checked here -- the binding checks them on the host (a malformed array cannot
+ * make a kernel write outside the outputs or d_ws).  Outputs, float32: d_f0 [F] (StoneMask's refined f0, 0 = unvoiced),
+ * d_sp [F, 513] (log10(sp / en), the record form), d_ap [F, 513], d_en [F].  An utterance's outputs depend only on its own
+ * samples (bit for bit, whatever its offset or neighbours in the batch).  Checked (VAENPVC_E_ARG): fs == 16000,
+ * 71 <= f0_floor < f0_ceil <= 800, 1 <= frame_period_ms <= 50, n_seg >= 1, n_seg <= S <= INT32_MAX,
+ * n_seg <= F <= (int)(1000 S / fs / frame_period_ms) + n_seg, no NULL pointer, no overlap of an output with an input,
+ * another output or the workspace.  d_ws: >= vaenpvc_analysis_workspace_bytes(...) bytes (VAENPVC_E_WORKSPACE if
+ * shorter or NULL), 256-byte aligned.  Its layout, every region starting at a 256-byte boundary in this order, with
+ * nb = 1 + (int)(log2(f0_ceil / f0_floor) * 2) bands, NBS = S + n_seg band samples and NES = S / 2 + 2 n_seg edge slots:
+ *   mean   double [n_seg]        mean of DIO's y = [x_u, 0] (S_u + 1 samples)
+ *   taps   double [nb, 1281]     combined low-cut x band-pass filter of band b, offsets -(320 + L_b) .. (320 + L_b)
+ *   band   double [nb, NBS]      band signal of utterance u at [b, soff[u] + u + i], i = 0 .. S_u
+ *   edges  double [nb, 4, NES]   fine edges (negative-going, positive-going, peak, dip) of utterance u from slot
+ *                                soff[u] / 2 + 2 u, in sample order
+ *   ecnt   int32  [nb, 4, n_seg] the number of fine edges of each list
+ *   cand   double [nb, F]        DIO candidate per band and frame (0: none)
+ *   score  double [nb, F]        its score / (candidate + 1e-12)
+ *   best   double [F]            the pre-fix contour (candidate of the best-scoring band)
+ *   s1, s2 double [F]            FixF0Contour scratch
+ *   f0d    double [F]            DIO's f0 (after FixF0Contour)
+ *   f0r    double [F]            StoneMask's refined f0 (d_f0 is its float32 cast)
+ *   ap0    double [F]            D4C LoveTrain's cumulative-power ratio (voiced when > 0.85)
+ *   coarse double [F]            D4C's coarse aperiodicity in dB after the f0 revision (0 where D4C's body did not run)
+ *   flags  int32  [F]            bit 0: StoneMask fell back to DIO's f0; bit 1: D4C's body ran */
+int64_t vaenpvc_analysis_workspace_bytes(int32_t n_seg, int64_t S, int64_t F, int32_t fs, double frame_period_ms,
+                                         double f0_floor, double f0_ceil);
+int vaenpvc_analyze(const float* d_x, const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t n_seg,
+                    int64_t S, int64_t F, int32_t fs, double frame_period_ms, double f0_floor, double f0_ceil,
+                    float* d_f0, float* d_sp, float* d_ap, float* d_en, void* d_ws, size_t ws_bytes, void* stream);
+
 /* analyzer.read record slicing (analyzer.py:113-127): rows of `rec_floats` float32
  * (1029) -> x = Tanhize(row[0:H]) and y = int64(row[rec_floats-1]) (bit-exact cast). */
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H,

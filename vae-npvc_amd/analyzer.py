@@ -5,11 +5,17 @@ The TF queue machinery is replaced by an HBM-resident frame store: every matchin
 uploaded once; a batch is ONE HIP kernel that gathers the shuffled record rows' sp columns,
 applies Tanhize and casts the speaker column to int64 (`vaenpvc_gather_unpack_records`); the shuffle
 order comes from a host-side BoundedShuffler with the reference queue's capacity /
-min_after_dequeue semantics.  WORLD feature
-extraction / synthesis (pyworld) is out of scope.
+min_after_dequeue semantics.
+
+Feature extraction (analyzer.py:25-72,189-193) runs on the device: `extract` / `extract_and_save_bin_to` read 16-bit
+PCM wavs with the standard `wave` module and hand them to `hipvae.world.analyze` (vaenpvc_analyze, WORLD-style
+DIO -> StoneMask -> CheapTrick -> D4C); `--batch_seconds` groups consecutive files into one device
+call.  Synthesis is convert.py --vocoder device.
 """
+import argparse
 import glob
 import os
+import wave
 
 import numpy as np
 import torch
@@ -23,6 +29,8 @@ FFT_SIZE = 1024
 SP_DIM = FFT_SIZE // 2 + 1
 FEAT_DIM = SP_DIM + SP_DIM + 1 + 1 + 1      # [sp, ap, f0, en, s]  (analyzer.py:21)
 RECORD_BYTES = FEAT_DIM * 4
+EPSILON = 1e-10                             # analyzer.py:15 (the en sum, applied on the device)
+SETS = ['Training Set', 'Testing Set']      # analyzer.py:16
 
 
 def load_npf(path, dtype=np.float32, count=SP_DIM):
@@ -319,3 +327,109 @@ def read_whole_features(file_pattern, num_epochs=1):
                 'speaker': v[:, SP_DIM * 2 + 2].astype(np.int64),
                 'filename': f.encode('utf8'),
             }
+
+
+def read_wav(path, fs=16000):
+    """librosa.load(path, sr=fs, mono=True) for 16-bit integer PCM at `fs`: int16 / 32768, channels averaged.
+    Other sample widths and rates raise ValueError (resampling is out of scope)."""
+    with wave.open(path, 'rb') as w:
+        nch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        raw = w.readframes(n)
+    if width != 2:
+        raise ValueError('%s: %d-bit samples; only 16-bit integer PCM is supported' % (path, 8 * width))
+    if rate != fs:
+        raise ValueError('%s: sampled at %d Hz, expected %d Hz (resample first)' % (path, rate, fs))
+    x = np.frombuffer(raw, '<i2').astype(np.float64) / 32768.0
+    x = x.reshape(-1, nch).mean(axis=1)
+    return x.astype(np.float32)
+
+
+def _analyze(xs, fs, f0_ceil):
+    """Device analysis of the waveforms xs (one call) -> one [T, 1028] float32 matrix [sp, ap, f0, en] per waveform."""
+    from hipvae import world
+    dev = torch.device('cuda', torch.cuda.current_device())
+    x = torch.from_numpy(np.concatenate(xs).astype(np.float32)).to(dev)
+    f0, sp, ap, en, frames = world.analyze(x, [len(v) for v in xs], fs=fs, f0_ceil=f0_ceil)
+    feat = torch.cat([sp, ap, f0[:, None], en[:, None]], 1).cpu().numpy()
+    out, o = [], 0
+    for T in frames:
+        out.append(feat[o:o + T])
+        o += T
+    return out
+
+
+def extract(filename, fs=16000, f0_ceil=500.0):
+    """analyzer.py:35-47: one wav -> [T, 1028] float32 rows [sp (log10, energy-normalised), ap, f0, en]."""
+    return _analyze([read_wav(filename, fs)], fs, f0_ceil)[0]
+
+
+def list_wavs(dir_to_wav):
+    """analyzer.py:50-60: (set, speaker, path) of every file under <set>/<speaker>/ for set in SETS and speaker in
+    SPEAKERS (other directories are skipped; sub-directories of a speaker directory too), in listing order."""
+    out = []
+    for d in sorted(os.listdir(dir_to_wav)):
+        if d not in SETS:
+            continue
+        for s in sorted(os.listdir(os.path.join(dir_to_wav, d))):
+            if s not in SPEAKERS:
+                continue
+            path = os.path.join(dir_to_wav, d, s)
+            for f in sorted(os.listdir(path)):
+                if not os.path.isdir(os.path.join(path, f)):
+                    out.append((d, s, os.path.join(path, f)))
+    return out
+
+
+def group_by_seconds(items, seconds, fs=16000):
+    """Consecutive (item, n_samples) pairs in groups of at most `seconds` of audio (a longer file goes alone;
+    seconds <= 0: every file alone).  Order is preserved."""
+    cap = int(seconds * fs)
+    groups, cur, n = [], [], 0
+    for it, k in items:
+        if cur and (cap <= 0 or n + k > cap):
+            groups.append(cur)
+            cur, n = [], 0
+        cur.append(it)
+        n += k
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def extract_and_save_bin_to(dir_to_bin, dir_to_wav, fs=16000, f0_ceil=500.0, batch_seconds=60.0):
+    """analyzer.py:50-72: <dir_to_bin>/<set>/<speaker>/<basename>.bin for every wav, records [sp, ap, f0, en, speaker]
+    written by write_bin.  Returns the written paths."""
+    todo = []
+    for d, s, path in list_wavs(dir_to_wav):
+        print(path)
+        x = read_wav(path, fs)
+        todo.append(((d, s, path, x), len(x)))
+    written = []
+    for group in group_by_seconds(todo, batch_seconds, fs):
+        feats = _analyze([g[3] for g in group], fs, f0_ceil)
+        for (d, s, path, _), ft in zip(group, feats):
+            b = os.path.splitext(os.path.basename(path))[0]
+            out = os.path.join(dir_to_bin, d, s, '{}.bin'.format(b))
+            write_bin(out, ft[:, :SP_DIM], ft[:, SP_DIM:2 * SP_DIM], ft[:, 2 * SP_DIM], ft[:, 2 * SP_DIM + 1], s)
+            written.append(out)
+    return written
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description='WORLD-style analysis of <set>/<speaker>/*.wav into .bin records')
+    p.add_argument('--dir_to_wav', default='./dataset/vcc2016/wav', help='Dir to *.wav')
+    p.add_argument('--dir_to_bin', default='./dataset/vcc2016/bin', help='Dir to output *.bin')
+    p.add_argument('--fs', type=int, default=16000, help='Global sampling frequency (only 16000)')
+    p.add_argument('--f0_ceil', type=float, default=500.0, help='Global f0 ceiling')
+    p.add_argument('--batch_seconds', type=float, default=60.0,
+                   help='seconds of audio per device call (consecutive files; <= 0: one file per call)')
+    a = p.parse_args(argv)
+    if a.fs != 16000:
+        p.error('--fs must be 16000 (resampling is out of scope)')
+    if not 71.0 < a.f0_ceil <= 800.0:
+        p.error('--f0_ceil must be in (71, 800]')
+    extract_and_save_bin_to(a.dir_to_bin, a.dir_to_wav, a.fs, a.f0_ceil, a.batch_seconds)
+
+
+if __name__ == '__main__':
+    main()

@@ -540,6 +540,63 @@ int vaenpvc_synthesize(const float* d_f0, const float* d_sp, const float* d_en, 
   return check_launch("synthesize");
 }
 
+static int analysis_bands(int32_t fs, double f0_floor, double f0_ceil) {
+  // 71 <= f0_floor < f0_ceil <= 800 at 16 kHz: every FFT the stages derive stays <= 2048 points
+  if (fs != 16000 || !std::isfinite(f0_floor) || !std::isfinite(f0_ceil) || !(f0_floor >= 71.0) ||
+      !(f0_floor < f0_ceil) || !(f0_ceil <= 800.0))
+    return -1;
+  return 1 + (int)(std::log(f0_ceil / f0_floor) / std::log(2.0) * 2.0);
+}
+
+static bool analysis_shape_ok(int32_t n_seg, int64_t S, int64_t F, double frame_period_ms, int32_t fs) {
+  // every utterance has >= 1 sample and >= 1 frame; F is at most the frame count the samples allow
+  return n_seg > 0 && n_seg < (1 << 24) && S >= n_seg && S <= INT32_MAX && F >= n_seg &&
+         std::isfinite(frame_period_ms) && frame_period_ms >= 1.0 && frame_period_ms <= 50.0 &&
+         F <= (int64_t)(1000.0 * (double)S / fs / frame_period_ms) + n_seg;
+}
+
+int64_t vaenpvc_analysis_workspace_bytes(int32_t n_seg, int64_t S, int64_t F, int32_t fs, double frame_period_ms,
+                                         double f0_floor, double f0_ceil) {
+  const int nb = analysis_bands(fs, f0_floor, f0_ceil);
+  if (nb < 1 || !analysis_shape_ok(n_seg, S, F, frame_period_ms, fs))
+    return fail(VAENPVC_E_ARG, "bad argument (n_seg %d, S %lld, F %lld, fs %d, frame period %g, f0 %g .. %g)", n_seg,
+                (long long)S, (long long)F, fs, frame_period_ms, f0_floor, f0_ceil);
+  return analysis_workspace_bytes(n_seg, S, F, nb);
+}
+
+int vaenpvc_analyze(const float* d_x, const int64_t* d_sample_offsets, const int64_t* d_frame_offsets, int32_t n_seg,
+                    int64_t S, int64_t F, int32_t fs, double frame_period_ms, double f0_floor, double f0_ceil,
+                    float* d_f0, float* d_sp, float* d_ap, float* d_en, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_x || !d_sample_offsets || !d_frame_offsets || !d_f0 || !d_sp || !d_ap || !d_en)
+    return fail(VAENPVC_E_ARG, "null argument");
+  const int nb = analysis_bands(fs, f0_floor, f0_ceil);
+  if (nb < 1) return fail(VAENPVC_E_ARG, "fs must be 16000 and 71 <= f0_floor < f0_ceil <= 800 (got %d, %g, %g)", fs,
+                          f0_floor, f0_ceil);
+  if (!analysis_shape_ok(n_seg, S, F, frame_period_ms, fs))
+    return fail(VAENPVC_E_ARG, "bad argument (n_seg %d, S %lld, F %lld, frame period %g)", n_seg, (long long)S,
+                (long long)F, frame_period_ms);
+  const int64_t nf = F * 4, nfh = F * 513 * 4, nx = S * 4, no = ((int64_t)n_seg + 1) * 8;
+  const void* outs[4] = {d_f0, d_sp, d_ap, d_en};
+  const int64_t outn[4] = {nf, nfh, nfh, nf};
+  for (int a = 0; a < 4; ++a) {
+    if (overlaps(outs[a], outn[a], d_x, nx) || overlaps(outs[a], outn[a], d_sample_offsets, no) ||
+        overlaps(outs[a], outn[a], d_frame_offsets, no))
+      return fail(VAENPVC_E_ARG, "outputs must not overlap an input");
+    for (int b = a + 1; b < 4; ++b)
+      if (overlaps(outs[a], outn[a], outs[b], outn[b])) return fail(VAENPVC_E_ARG, "outputs must not overlap");
+  }
+  const int64_t need = analysis_workspace_bytes(n_seg, S, F, nb);
+  if (d_ws == nullptr || ws_bytes < (size_t)need)
+    return fail(VAENPVC_E_WORKSPACE, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                (long long)ws_bytes);
+  if (((uintptr_t)d_ws & 255) != 0) return fail(VAENPVC_E_ARG, "workspace must be 256-byte aligned");
+  for (int a = 0; a < 4; ++a)
+    if (overlaps(outs[a], outn[a], d_ws, need)) return fail(VAENPVC_E_ARG, "outputs must not overlap the workspace");
+  launch_analyze(d_x, d_sample_offsets, d_frame_offsets, n_seg, S, F, fs, frame_period_ms, f0_floor, f0_ceil, nb, d_f0,
+                 d_sp, d_ap, d_en, d_ws, (hipStream_t)stream);
+  return check_launch("analyze");
+}
+
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H, const float* d_xmin,
                            const float* d_xmax, float* d_x, int64_t* d_y, void* stream) {
   if (!d_records || !d_xmin || !d_xmax || !d_x || !d_y || F < 1 || H < 1 || rec_floats < H + 1)

@@ -112,6 +112,26 @@ void launch_synthesize(const float* f0, const float* sp, const float* en, const 
                        const int64_t* soff, int n_seg, int64_t F, int64_t S, int fs, double frame_period_ms,
                        uint64_t seed, float* y, void* ws, hipStream_t s);
 
+// ---- WORLD-style feature analysis of the data path (gfx950_analysis.hip) ---------
+// workspace regions (include/vaenpvc.h documents the layout, 256-byte aligned, in this order)
+struct AnalysisWs {
+  double* mean;     // [n_seg]
+  double* taps;     // [nb, analysis_taps()]
+  double* band;     // [nb, S + n_seg]
+  double* edges;    // [nb, 4, S / 2 + 2 n_seg]
+  int32_t* ecnt;    // [nb, 4, n_seg]
+  double *cand, *score;  // [nb, F]
+  double *best, *s1, *s2, *f0d, *f0r, *ap0, *coarse;  // [F]
+  int32_t* flags;   // [F]
+  int64_t bytes;
+};
+AnalysisWs analysis_carve(void* ws, int n_seg, int64_t S, int64_t F, int nb);
+int analysis_taps();
+int64_t analysis_workspace_bytes(int n_seg, int64_t S, int64_t F, int nb);
+void launch_analyze(const float* x, const int64_t* soff, const int64_t* foff, int n_seg, int64_t S, int64_t F, int fs,
+                    double frame_period_ms, double f0_floor, double f0_ceil, int nb, float* f0, float* sp, float* ap,
+                    float* en, void* ws, hipStream_t s);
+
 // ---- tuned gfx950 kernels for the VCC2016 geometry (gfx950_*.hip) ----------------
 namespace tuned {
 // step masks: bit set = use the tuned kernel for that step, clear = generic kernel.

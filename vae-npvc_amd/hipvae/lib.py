@@ -75,6 +75,9 @@ SIGNATURES = {
     'vaenpvc_synth_workspace_bytes': (_I64, [_I32, _I64, _I32, _I32]),
     'vaenpvc_synthesize': (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I64, _I32, _I32, C.c_double, _U64, _P, _P,
                                      C.c_size_t, _P]),
+    'vaenpvc_analysis_workspace_bytes': (_I64, [_I32, _I64, _I64, _I32, C.c_double, C.c_double, C.c_double]),
+    'vaenpvc_analyze': (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                                  _P, C.c_size_t, _P]),
     'vaenpvc_unpack_records': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_gather_unpack_records': (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_set_precision': (C.c_int, [_P, C.c_int]),
