@@ -351,6 +351,61 @@ int vaenpvc_analyze(const float* d_x, const int64_t* d_sample_offsets, const int
                     int64_t S, int64_t F, int32_t fs, double frame_period_ms, double f0_floor, double f0_ceil,
                     float* d_f0, float* d_sp, float* d_ap, float* d_en, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Objective evaluation (not in the reference; evaluate.py): mel-cepstral distortion in dB between two utterances along
+ * their dynamic-time-warping path, with the log-F0 error and the voicing mismatch on the same path.  The definition is
+ * DESIGN.md section 16, restated by tests/mcd_ref.py.  Inputs per side are what a .bin record holds, float32: sp [F, 513]
+ * = log10(sp / en), en [F] (> 0), f0 [F] (voiced when > 1).  All arithmetic is float64.
+ *
+ * vaenpvc_mcep_matrix (host only, no device work): fills host_W, double [(order + 1) x H] row-major, the fixed matrix with
+ * mc[t] = W L[t] for the log amplitude L[t, k] = 0.5 (ln 10 sp[t, k] + ln en[t]): the one-sided real cepstrum of the
+ * 1024-point symmetric extension of L, then SPTK's freqt recursion (all-pass constant alpha) from 513 coefficients to
+ * order + 1, so that L(omega) ~ sum_m mc[m] cos(m w(omega)), w the all-pass phase.  VAENPVC_E_ARG unless H == 513,
+ * 1 <= order <= VAENPVC_MCD_MAX_ORDER, 0 <= alpha < 1, host_W != NULL.  The caller uploads W for vaenpvc_mcd_dtw.
+ *
+ * vaenpvc_mcd_dtw: n_pair utterance pairs; pair p is frames d_offA[p] .. d_offA[p+1] of side A (Ta frames) and
+ * d_offB[p] .. d_offB[p+1] of side B (Tb frames); both offset arrays are device int64 [n_pair + 1], non-decreasing,
+ * [0] = 0, [n_pair] = Fa resp. Fb, every utterance 1 .. VAENPVC_MCD_MAX_FRAMES frames; cells = sum over pairs of
+ * Ta * Tb.  The offsets are NOT checked on the host -- the binding does that; on the device a pair that breaks the
+ * contract (or does not fit into `cells`) is skipped and its results are NaN, nothing is written out of bounds.
+ *   local cost  d(i, j) = sqrt(sum_{m=1..order} (mcA[i, m] - mcB[j, m])^2)           (the gain mc[0] is left out)
+ *   DTW         D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), D(0, 0) = d(0, 0), unit weights, no band; on
+ *               equal values the predecessor is the diagonal, then (i-1, j), then (i, j-1)
+ * d_results: double [n_pair, 8] = { mcd_db = (VAENPVC_MCD_DB_FACTOR * sum) / P,  P (path length),  D(Ta-1, Tb-1),
+ * lf0_rmse = sqrt(mean((ln f0A - ln f0B)^2)) over the path cells where both frames are voiced (NaN if none),  the number
+ * of those cells,  the number of path cells where exactly one frame is voiced,  sum = the sum of d over the path,  0 };
+ * sums run in back-trace order, from (Ta-1, Tb-1) to (0, 0), one rounding per operation.
+ * d_path (optional, NULL to skip): int32 [Fa + Fb, 2]; pair p's path starts at entry d_offA[p] + d_offB[p], P entries
+ * (i, j) in back-trace order, first (Ta-1, Tb-1), last (0, 0); the rest of the pair's Ta + Tb entries is not written.
+ * d_D (optional, NULL to skip): double [cells], the accumulated cost D in the layout of the `cost` region below.
+ * A pair's results depend only on its own frames (bit for bit, whatever its place or neighbours in the call).
+ * Checked (VAENPVC_E_ARG): 1 <= n_pair <= VAENPVC_MCD_MAX_PAIRS, n_pair <= Fa, Fb <= n_pair * VAENPVC_MCD_MAX_FRAMES,
+ * max(Fa, Fb) <= cells <= min(Fa * Fb, n_pair * VAENPVC_MCD_MAX_FRAMES^2), 1 <= order <= VAENPVC_MCD_MAX_ORDER, no NULL
+ * pointer besides the optional ones, no overlap of an output with an input, another output or the workspace.  d_ws:
+ * >= vaenpvc_mcd_workspace_bytes(...) bytes (VAENPVC_E_WORKSPACE if shorter or NULL), 256-byte aligned.  Its layout,
+ * every region starting at a 256-byte boundary in this order:
+ *   mc     double [Fa + Fb, order + 1]  mel-cepstra, side A's frames first
+ *   lf0    double [Fa + Fb]             ln f0 where f0 > 1, otherwise -1
+ *   pinfo  int64  [n_pair + 1, 6]       per pair: first cell of its cost matrix, first tile, d_offA[p], d_offB[p], Ta, Tb
+ *                                       (Ta = Tb = 0: skipped); row n_pair holds the totals
+ *   cost   double [cells]               d, pair after pair (Ta * Tb cells each; element offsets are 64-bit); inside a pair
+ *                                       anti-diagonal after anti-diagonal: s = i + j ascending, i ascending inside a
+ *                                       diagonal, so the DP's lanes touch consecutive addresses.  With m = min(Ta, Tb),
+ *                                       M = max(Ta, Tb) the cells before diagonal s number s (s + 1) / 2 for s <= m,
+ *                                       m (m + 1) / 2 + (s - m) m for m <= s <= M, Ta Tb - r (r + 1) / 2 with
+ *                                       r = Ta + Tb - 1 - s beyond; cell (i, j) follows at i - max(0, s - Tb + 1)
+ *                                       (hipvae.metrics.diag_index)
+ *   code   uint8  [cells]               predecessor of each cell, same layout: 0 diagonal, 1 (i-1, j), 2 (i, j-1) */
+#define VAENPVC_MCD_MAX_FRAMES 4096
+#define VAENPVC_MCD_MAX_ORDER 64
+#define VAENPVC_MCD_MAX_PAIRS 65536
+#define VAENPVC_MCD_DB_FACTOR 6.1418514637137541 /* 10 sqrt(2) / ln 10 */
+int vaenpvc_mcep_matrix(int32_t order, double alpha, int32_t H, double* host_W);
+int64_t vaenpvc_mcd_workspace_bytes(int32_t n_pair, int64_t Fa, int64_t Fb, int64_t cells, int32_t order);
+int vaenpvc_mcd_dtw(const float* d_spA, const float* d_enA, const float* d_f0A, const int64_t* d_offA, int64_t Fa,
+                    const float* d_spB, const float* d_enB, const float* d_f0B, const int64_t* d_offB, int64_t Fb,
+                    int32_t n_pair, int64_t cells, const double* d_W, int32_t order, double* d_results,
+                    int32_t* d_path, double* d_D, void* d_ws, size_t ws_bytes, void* stream);
+
 /* analyzer.read record slicing (analyzer.py:113-127): rows of `rec_floats` float32
  * (1029) -> x = Tanhize(row[0:H]) and y = int64(row[rec_floats-1]) (bit-exact cast). */
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H,

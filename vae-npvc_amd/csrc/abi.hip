@@ -597,6 +597,65 @@ int vaenpvc_analyze(const float* d_x, const int64_t* d_sample_offsets, const int
   return check_launch("analyze");
 }
 
+int vaenpvc_mcep_matrix(int32_t order, double alpha, int32_t H, double* host_W) {
+  if (!host_W) return fail(VAENPVC_E_ARG, "null argument");
+  if (order < 1 || order > VAENPVC_MCD_MAX_ORDER || H != 513 || !std::isfinite(alpha) || !(alpha >= 0.0) ||
+      !(alpha < 1.0))
+    return fail(VAENPVC_E_ARG, "need 1 <= order <= %d, 0 <= alpha < 1, H == 513 (got %d, %g, %d)",
+                VAENPVC_MCD_MAX_ORDER, order, alpha, H);
+  mcep_matrix_host(order, alpha, host_W);
+  return 0;
+}
+
+static bool mcd_shape_ok(int32_t n_pair, int64_t Fa, int64_t Fb, int64_t cells, int32_t order) {
+  // every utterance has 1 .. VAENPVC_MCD_MAX_FRAMES frames, so cells (the sum of Ta * Tb) lies between the larger side's
+  // frame count and n_pair * MAX^2; the offsets themselves are device data (checked by the binding and by k_mcd_prep)
+  const int64_t mx = VAENPVC_MCD_MAX_FRAMES;
+  return n_pair >= 1 && n_pair <= VAENPVC_MCD_MAX_PAIRS && Fa >= n_pair && Fb >= n_pair && Fa <= n_pair * mx &&
+         Fb <= n_pair * mx && cells >= (Fa > Fb ? Fa : Fb) && cells <= Fa * Fb && cells <= n_pair * mx * mx &&
+         order >= 1 && order <= VAENPVC_MCD_MAX_ORDER;
+}
+
+int64_t vaenpvc_mcd_workspace_bytes(int32_t n_pair, int64_t Fa, int64_t Fb, int64_t cells, int32_t order) {
+  if (!mcd_shape_ok(n_pair, Fa, Fb, cells, order))
+    return fail(VAENPVC_E_ARG, "bad argument (n_pair %d, Fa %lld, Fb %lld, cells %lld, order %d)", n_pair,
+                (long long)Fa, (long long)Fb, (long long)cells, order);
+  return mcd_workspace_bytes(n_pair, Fa, Fb, cells, order);
+}
+
+int vaenpvc_mcd_dtw(const float* d_spA, const float* d_enA, const float* d_f0A, const int64_t* d_offA, int64_t Fa,
+                    const float* d_spB, const float* d_enB, const float* d_f0B, const int64_t* d_offB, int64_t Fb,
+                    int32_t n_pair, int64_t cells, const double* d_W, int32_t order, double* d_results,
+                    int32_t* d_path, double* d_D, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_spA || !d_enA || !d_f0A || !d_offA || !d_spB || !d_enB || !d_f0B || !d_offB || !d_W || !d_results)
+    return fail(VAENPVC_E_ARG, "null argument");
+  if (!mcd_shape_ok(n_pair, Fa, Fb, cells, order))
+    return fail(VAENPVC_E_ARG, "bad argument (n_pair %d, Fa %lld, Fb %lld, cells %lld, order %d)", n_pair,
+                (long long)Fa, (long long)Fb, (long long)cells, order);
+  const int64_t need = mcd_workspace_bytes(n_pair, Fa, Fb, cells, order);
+  if (d_ws == nullptr || ws_bytes < (size_t)need)
+    return fail(VAENPVC_E_WORKSPACE, "workspace too small: need %lld bytes, got %lld", (long long)need,
+                (long long)ws_bytes);
+  if (((uintptr_t)d_ws & 255) != 0) return fail(VAENPVC_E_ARG, "workspace must be 256-byte aligned");
+  const void* outs[3] = {d_results, d_path, d_D};
+  const int64_t outn[3] = {(int64_t)n_pair * 64, (Fa + Fb) * 8, cells * 8};
+  const void* ins[9] = {d_spA, d_enA, d_f0A, d_offA, d_spB, d_enB, d_f0B, d_offB, d_W};
+  const int64_t inn[9] = {Fa * 513 * 4, Fa * 4, Fa * 4, ((int64_t)n_pair + 1) * 8, Fb * 513 * 4, Fb * 4, Fb * 4,
+                          ((int64_t)n_pair + 1) * 8, ((int64_t)order + 1) * 513 * 8};
+  for (int a = 0; a < 3; ++a) {
+    if (!outs[a]) continue;
+    for (int b = 0; b < 9; ++b)
+      if (overlaps(outs[a], outn[a], ins[b], inn[b])) return fail(VAENPVC_E_ARG, "outputs must not overlap an input");
+    for (int b = a + 1; b < 3; ++b)
+      if (outs[b] && overlaps(outs[a], outn[a], outs[b], outn[b]))
+        return fail(VAENPVC_E_ARG, "outputs must not overlap");
+    if (overlaps(outs[a], outn[a], d_ws, need)) return fail(VAENPVC_E_ARG, "outputs must not overlap the workspace");
+  }
+  launch_mcd_dtw(d_spA, d_enA, d_f0A, d_offA, Fa, d_spB, d_enB, d_f0B, d_offB, Fb, n_pair, cells, d_W, order, d_results,
+                 d_path, d_D, d_ws, (hipStream_t)stream);
+  return check_launch("mcd_dtw");
+}
+
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H, const float* d_xmin,
                            const float* d_xmax, float* d_x, int64_t* d_y, void* stream) {
   if (!d_records || !d_xmin || !d_xmax || !d_x || !d_y || F < 1 || H < 1 || rec_floats < H + 1)

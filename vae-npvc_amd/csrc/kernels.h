@@ -132,6 +132,25 @@ void launch_analyze(const float* x, const int64_t* soff, const int64_t* foff, in
                     double frame_period_ms, double f0_floor, double f0_ceil, int nb, float* f0, float* sp, float* ap,
                     float* en, void* ws, hipStream_t s);
 
+// ---- DTW-aligned mel-cepstral distortion (gfx950_dtw.hip) ----
+constexpr int MCD_MAX_FRAMES = 4096;                     // per utterance and side (= VAENPVC_MCD_MAX_FRAMES)
+constexpr double MCD_DB_FACTOR = 6.1418514637137541;     // 10 sqrt(2) / ln 10 (= VAENPVC_MCD_DB_FACTOR)
+struct McdWs {      // the regions of include/vaenpvc.h, in this order, each 256-byte aligned
+  double* mc;           // [Fa + Fb, order + 1]
+  double* lf0;          // [Fa + Fb]
+  int64_t* pinfo;       // [n_pair + 1, 6]
+  double* cost;         // [cells]
+  unsigned char* code;  // [cells]
+  int64_t bytes;
+};
+McdWs mcd_carve(void* ws, int n_pair, int64_t Fa, int64_t Fb, int64_t cells, int order);
+int64_t mcd_workspace_bytes(int n_pair, int64_t Fa, int64_t Fb, int64_t cells, int order);
+void mcep_matrix_host(int order, double alpha, double* W);      // host only: W [(order + 1) x 513]
+void launch_mcd_dtw(const float* spA, const float* enA, const float* f0A, const int64_t* offA, int64_t Fa,
+                    const float* spB, const float* enB, const float* f0B, const int64_t* offB, int64_t Fb, int n_pair,
+                    int64_t cells, const double* W, int order, double* results, int32_t* path, double* D, void* ws,
+                    hipStream_t s);
+
 // ---- tuned gfx950 kernels for the VCC2016 geometry (gfx950_*.hip) ----------------
 namespace tuned {
 // step masks: bit set = use the tuned kernel for that step, clear = generic kernel.

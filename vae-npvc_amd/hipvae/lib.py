@@ -78,6 +78,10 @@ SIGNATURES = {
     'vaenpvc_analysis_workspace_bytes': (_I64, [_I32, _I64, _I64, _I32, C.c_double, C.c_double, C.c_double]),
     'vaenpvc_analyze': (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
                                   _P, C.c_size_t, _P]),
+    'vaenpvc_mcep_matrix': (C.c_int, [_I32, C.c_double, _I32, _P]),
+    'vaenpvc_mcd_workspace_bytes': (_I64, [_I32, _I64, _I64, _I64, _I32]),
+    'vaenpvc_mcd_dtw': (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _P, _P, _P, _P,
+                                  C.c_size_t, _P]),
     'vaenpvc_unpack_records': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_gather_unpack_records': (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_set_precision': (C.c_int, [_P, C.c_int]),
