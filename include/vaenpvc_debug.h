@@ -15,38 +15,50 @@
 extern "C" {
 #endif
 
-/* Debug/validation hook (no reference counterpart): per-step selection between the tuned
- * gfx950 kernel (bit set) and the geometry-generic kernel (bit clear) when the context
- * runs in VAENPVC_IMPL_AUTO on the VCC2016 geometry.  Bits 0..4 = encoder conv i,
- * 5 = heads, 6 = merge, 7..10 = decoder layer i; one mask for forward steps, one for
- * backward steps.  Default: all ones.  State of THIS context.
- * Bit 30 of the forward mask (default set): cleared = use the bf16-split kernels of the last decoder layer at
- * any batch size (they are selected at >= 16 frames otherwise; parity tests).  Bit 30 of the backward mask
- * (default set): cleared = launch the weight-gradient kernels on the caller's stream instead of the context's
- * helper stream (serialised kernels; used by bench.py to time single kernels).
- * Bit 29 of either mask (default set): cleared = keep the dense-shaped layers (heads, merge, encoder layer 4) on the
- * exact-fp32 MFMA kernels instead of the bf16-split plane GEMM kernels, which are selected at >= 1024 frames;
- * bit 28 (default set): cleared = select them at any batch size (parity tests).
- * Bit 27 (default set): cleared = no conv site on the view-GEMM kernels; bit 26 (default set): cleared = EVERY conv
- * site of encoder layers 1-3 / decoder layers 0-2 on the view GEMMs instead of the measured per-precision site set.
- * Bits 25 / 22 (default set): cleared = every thin / medium conv site on the fused kernels (gfx950_fconv.h,
- * gfx950_fconv_r.h) at any batch size; bit 24 of the backward mask: the thin weight gradients on gfx950_fwgrad.h;
- * bit 23: encoder layer 0 on its wave-per-frame kernels.  (The bits 22-28 exist for the parity tests, which pin every
- * kernel family against the float64 restatement at small batch sizes; defaults select by measurement.)
- * Bit 21 of either mask (default set): cleared = never use the small-batch frame kernels (gfx950_frame.h: one workgroup
- * carries one frame through a whole pass; selected up to 512 frames per call, VAENPVC_FRAME_MAX); a train step uses them
- * for both passes or for neither.  Bit 20 of the backward mask (default set): cleared = behind the frame kernels, the
- * weight gradients come from the layered kernels on two streams instead of the one-launch job list
- * (gfx950_frame_wgrad.h).  Bit 18 of the backward mask (default set): cleared = a small-batch train step keeps the 1025-tap
- * layer inside the two frame kernels instead of the two eight-workgroups-per-frame launches between them.  Bit 19 of the backward mask (default set): cleared = encoder layer 0's LayerNorm backward
- * and weight gradient as two passes instead of the fused kernel (k_enc0_bwd_wave, from 1024 frames on).  Bit 17 of the
- * backward mask (default set): cleared = the 1025-tap layer's weight gradient on the eight-wave kernel (64 x 64 wave tiles,
- * k_toep_wgrad_bf16_k32) at every batch size instead of the four-wave kernel (128 x 128 wave tiles, operands by LDS-DMA:
- * k_toep_wgrad_bf16_w4) from 4 096 frames on; bit 16 likewise for the dense-shaped weight gradients with many tiles per row
- * chunk (encoder layer 4: k_gemm_tn4 instead of k_gemm_tn).  Bit 15 of the backward mask (default set): cleared = the thin
- * layers' backward steps (decoder layers 2 and 1, encoder layer 1; environment VAENPVC_FB_LAYERS = bit set of those three) as three
- * kernels each (LayerNorm backward, input gradient, weight gradient) instead of ONE kernel per layer (csrc/gfx950_fbwd.h, from 1 024
- * frames on); bit 14 (default set): cleared = those one-kernel steps at any batch size (parity tests).
+/* Bits of the two kernel-selection masks (vaenpvc_set_tuned_masks): one mask for the forward steps, one for the backward
+ * steps, default all ones, state of THIS context.  A cleared bit moves that step of that pass off the measured default;
+ * the *_MIN_FRAMES bits exist for the parity tests, which pin every kernel family at small batch sizes. */
+enum vaenpvc_sel_bit {
+  VAENPVC_SEL_ENC0 = 0,                 /* 0..10, one bit per step: cleared = the geometry-generic kernel instead of the tuned gfx950 one */
+  VAENPVC_SEL_ENC1 = 1,
+  VAENPVC_SEL_ENC2 = 2,
+  VAENPVC_SEL_ENC3 = 3,
+  VAENPVC_SEL_ENC4 = 4,
+  VAENPVC_SEL_HEADS = 5,
+  VAENPVC_SEL_MERGE = 6,
+  VAENPVC_SEL_DEC0 = 7,
+  VAENPVC_SEL_DEC1 = 8,
+  VAENPVC_SEL_DEC2 = 9,
+  VAENPVC_SEL_DEC3 = 10,
+  VAENPVC_SEL_FBWD_MIN_FRAMES = 14,     /* backward: cleared = the one-kernel backward steps at any batch size (from 1 024 frames on otherwise) */
+  VAENPVC_SEL_FBWD = 15,                /* backward: cleared = the thin layers' backward steps (decoder 2 and 1, encoder 1; VAENPVC_FB_LAYERS) as three
+                                           kernels each instead of ONE kernel per layer (csrc/gfx950_fbwd.h) */
+  VAENPVC_SEL_TN_W4 = 16,               /* backward: cleared = dense-shaped weight gradients with many tiles per row chunk (encoder layer 4) on
+                                           k_gemm_tn instead of the four-wave k_gemm_tn4 */
+  VAENPVC_SEL_TAP_WGRAD_W4 = 17,        /* backward: cleared = the 1025-tap layer's weight gradient on the eight-wave kernel (k_toep_wgrad_bf16_k32) at
+                                           every batch size instead of the four-wave one (k_toep_wgrad_bf16_w4) from 4 096 frames on */
+  VAENPVC_SEL_FRAME_SPLIT = 18,         /* backward: cleared = a small-batch train step keeps the 1025-tap layer inside the two frame kernels */
+  VAENPVC_SEL_ENC0_FUSED_BWD = 19,      /* backward: cleared = encoder layer 0's LayerNorm backward and weight gradient as two passes instead of
+                                           k_enc0_bwd_wave (from 1 024 frames on) */
+  VAENPVC_SEL_FRAME_WGRAD = 20,         /* backward: cleared = behind the frame kernels, the layered weight-gradient kernels on two streams instead of
+                                           the one-launch job list (csrc/gfx950_frame_wgrad.h) */
+  VAENPVC_SEL_FRAME = 21,               /* cleared = never the small-batch frame kernels (csrc/gfx950_frame.h; selected up to VAENPVC_FRAME_MAX = 512
+                                           frames per call); a train step uses them for both passes or for neither */
+  VAENPVC_SEL_FCONV_R_MIN_FRAMES = 22,  /* cleared = every medium conv site on the register-weight fused kernel (csrc/gfx950_fconv_r.h) at any batch size */
+  VAENPVC_SEL_ENC0_WAVE_MIN_FRAMES = 23, /* cleared = encoder layer 0 on its wave-per-frame kernels at any batch size */
+  VAENPVC_SEL_FWGRAD_MIN_FRAMES = 24,   /* backward: cleared = every thin weight gradient on the fused kernel (csrc/gfx950_fwgrad.h) at any batch size */
+  VAENPVC_SEL_FCONV_MIN_FRAMES = 25,    /* cleared = every thin conv site on the fused kernel (csrc/gfx950_fconv.h) at any batch size */
+  VAENPVC_SEL_CV_SITE_SET = 26,         /* cleared = EVERY conv site of encoder layers 1-3 / decoder layers 0-2 on the view GEMMs instead of the
+                                           measured per-precision site set */
+  VAENPVC_SEL_VIEW_GEMM = 27,           /* cleared = no conv site on the view-GEMM kernels (csrc/gfx950_viewconv.h) */
+  VAENPVC_SEL_PLANE_GEMM_MIN_FRAMES = 28, /* cleared = the plane GEMM and view-GEMM kernels at any batch size (from 1 024 frames on otherwise) */
+  VAENPVC_SEL_PLANE_GEMM = 29,          /* cleared = heads, merge and encoder layer 4 on the exact-fp32 MFMA kernels instead of the bf16-split plane GEMMs */
+  VAENPVC_SEL_TOEP_MIN_FRAMES = 30,     /* forward: cleared = the bf16-split kernels of the last decoder layer at any batch size (from 16 frames on otherwise) */
+  VAENPVC_SEL_WGRAD_STREAM = 30         /* backward: cleared = the weight-gradient kernels on the caller's stream instead of the context's helper
+                                           stream (serialised kernels; bench.py times single kernels this way) */
+};
+/* Debug/validation hook (no reference counterpart): sets both masks of a context that runs in VAENPVC_IMPL_AUTO on the
+ * VCC2016 geometry.
  * vaenpvc_timer_select accepts a comma-separated LIST of site tags (a kernel group timed in one pass: bench.py's roofline.sites). */
 int vaenpvc_set_tuned_masks(vaenpvc_ctx* ctx, uint32_t fwd_mask, uint32_t bwd_mask);
 

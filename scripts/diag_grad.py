@@ -9,7 +9,7 @@ for p in (ROOT, os.path.join(ROOT, 'vae-npvc_amd'), os.path.join(ROOT, 'tests'))
     sys.path.insert(0, p)
 from helpers import load_arch, sample_idx, GOLDEN, golden_large_inputs  # noqa: E402
 from oracle import convvae_oracle as O  # noqa: E402
-from hipvae import Engine  # noqa: E402
+from hipvae import Engine, lib as L  # noqa: E402
 
 F, seed = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (8192, 21)
 arch = load_arch()
@@ -17,8 +17,8 @@ gold = np.load(os.path.join(GOLDEN, 'vcc2016_F%d_seed%d.npz' % (F, seed)))
 P = O.init_params(arch, seed)
 x, y, eps = golden_large_inputs(arch, gold, F, seed)
 CFG = [('generic kernels', dict(precision='bf16x3', impl='generic'), (0xffffffff, 0xffffffff), {}),
-       ('fp32, no side stream', dict(precision='bf16x3'), (0x9fffffff | (1 << 30), 0x9fffffff), {'VAENPVC_TOEP': 'f32'}),
-       ('fp32 kernels only', dict(precision='bf16x3'), (0x9fffffff | (1 << 30), 0x9fffffff | (1 << 30)), {'VAENPVC_TOEP': 'f32'}),
+       ('fp32, no side stream', dict(precision='bf16x3'), (0x9fffffff | (1 << L.SEL_TOEP_MIN_FRAMES), 0x9fffffff), {'VAENPVC_TOEP': 'f32'}),
+       ('fp32 kernels only', dict(precision='bf16x3'), (0x9fffffff | (1 << L.SEL_TOEP_MIN_FRAMES), 0x9fffffff | (1 << L.SEL_WGRAD_STREAM)), {'VAENPVC_TOEP': 'f32'}),
        ('toep x3, dense fp32', dict(precision='bf16x3'), (0xdfffffff, 0xdfffffff), {}),
        ('toep x2, dense fp32', dict(precision='auto'), (0xdfffffff, 0xdfffffff), {}),
        ('toep x3, dense x3', dict(precision='bf16x3'), (0xffffffff, 0xffffffff), {}),

@@ -16,7 +16,7 @@ import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'vae-npvc_amd'))
 import torch
-from hipvae import Engine
+from hipvae import Engine, lib as L
 from hipvae.dp import Stepper
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 300
@@ -28,7 +28,7 @@ F = 16
 x = torch.tanh(torch.randn(F, 513, generator=g)).cuda()
 y = torch.randint(0, 10, (F,), generator=g).cuda()
 eps = torch.randn(F, 128, generator=g).cuda()
-MASK = {'frame': 0xffffffff, 'layered': 0xffffffff & ~(1 << 21)}
+MASK = {'frame': 0xffffffff, 'layered': 0xffffffff & ~(1 << L.SEL_FRAME)}
 lines = []
 
 

@@ -7,13 +7,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'vae-npvc_amd'))
 import torch
-from hipvae import Engine
+from hipvae import Engine, lib as L
 
 TAG = os.environ.get('W4_TAG', 'dec3_wgrad')
 arch = json.load(open(os.path.join(ROOT, 'vae-npvc_amd', 'architecture-vae-vcc2016.json')))
 eng = Engine(arch)
 eng.init_params(0)
-eng.set_tuned_masks(0xffffffff, 0xffffffff & ~(1 << 30))      # weight gradients on the caller's stream: serialised kernels
+eng.set_tuned_masks(0xffffffff, 0xffffffff & ~(1 << L.SEL_WGRAD_STREAM))      # weight gradients on the caller's stream: serialised kernels
 sizes = [int(a) for a in sys.argv[1:]] or [4096, 8192, 16384, 32768]
 g = torch.Generator().manual_seed(0)
 for F in sizes:

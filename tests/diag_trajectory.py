@@ -17,12 +17,13 @@ from oracle import convvae_oracle as O
 from test_gpu_parity import ARCHS, KINK_TAU, gpu_branches
 from test_gpu_frame import oracle_adam_trajectory
 from hipvae import Engine
+from hipvae.lib import SEL_FRAME
 from hipvae.dp import Stepper
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 F = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 arch = ARCHS['vcc']
-FRAME = 1 << 21
+FRAME = 1 << SEL_FRAME
 CONFIGS = [('generic', 0xffffffff & ~FRAME, None, 'generic'), ('layered bf16x2', 0xffffffff & ~FRAME, None, 'auto'),
            ('frame', 0xffffffff, None, 'auto')]
 P0, P1, (x, y, eps), want = oracle_adam_trajectory(arch, F, 3, N)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from helpers import rel_err
+from hipvae.lib import SEL_FRAME, SEL_FRAME_SPLIT, SEL_FRAME_WGRAD
 from oracle import convvae_oracle as O
 from test_gpu_parity import (ARCHS, TOL_ACT, TOL_GRAD, check, compare_everything, make_engine, oracle_case, report,
                              run_train, upload)
@@ -26,7 +27,7 @@ def test_frame_path_every_tensor_and_gradient(F, seed):
 def test_frame_passes_with_the_layered_weight_gradients():
     """bit 20 of the backward mask cleared: the frame passes feed the LAYERED weight-gradient kernels (two streams)
     instead of the one-launch job list -- the A/B partner of the default, kept correct"""
-    eng = make_engine('vcc', 'auto', masks=(0xffffffff, 0xffffffff & ~(1 << 20)), frame=True)
+    eng = make_engine('vcc', 'auto', masks=(0xffffffff, 0xffffffff & ~(1 << SEL_FRAME_WGRAD)), frame=True)
     fails = compare_everything(eng, 16, 3, 'frame F16 layered-wgrad ')
     assert not fails, '\n'.join(fails)
 
@@ -35,7 +36,7 @@ def test_frame_step_with_the_tap_layer_inside_the_frame_kernels():
     """bit 18 of the backward mask cleared: the 1025-tap layer, the log-density and d(xh) inside the two frame kernels (the
     form the encode / decode / loss entry points always use) instead of the eight-workgroups-per-frame launches between them
     -- the A/B partner of the default train step, kept correct"""
-    eng = make_engine('vcc', 'auto', masks=(0xffffffff, 0xffffffff & ~(1 << 18)), frame=True)
+    eng = make_engine('vcc', 'auto', masks=(0xffffffff, 0xffffffff & ~(1 << SEL_FRAME_SPLIT)), frame=True)
     fails = compare_everything(eng, 16, 3, 'frame F16 unsplit ')
     assert not fails, '\n'.join(fails)
 
@@ -53,7 +54,7 @@ def test_frame_path_is_what_runs_by_default_and_can_be_switched_off():
     ms, n = eng.timer_read()
     eng.timer_select(None)
     assert n == 1, 'the frame forward kernel did not run at 16 frames with default settings'
-    eng.set_tuned_masks(0xffffffff & ~(1 << 21), 0xffffffff & ~(1 << 21))
+    eng.set_tuned_masks(0xffffffff & ~(1 << SEL_FRAME), 0xffffffff & ~(1 << SEL_FRAME))
     eng.timer_select('frame_fwd')
     l_b, g_b = run_train(eng, P, x, y, eps)
     _, n = eng.timer_read()
@@ -288,7 +289,7 @@ def test_twenty_adam_steps_follow_the_float64_oracle(path):
     #  ~0 as training proceeds, leave the per-tensor bar after ~15 steps: 3.6e-4 of the tensor's largest entry, measured)
     eng = Engine(arch, precision={'frame': None, 'layered': 'bf16x3', 'layered-bf16x2': 'bf16x2'}[path])
     sum_scaled = path == 'layered-bf16x2'
-    mask = 0xffffffff if path == 'frame' else 0xffffffff & ~(1 << 21)
+    mask = 0xffffffff if path == 'frame' else 0xffffffff & ~(1 << SEL_FRAME)
     eng.set_tuned_masks(mask, mask)
     eng.load_flat(O.flatten_params(P0))
     xt, yt, et = (torch.tensor(a, device=eng.device) for a in (x, y, eps))

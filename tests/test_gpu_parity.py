@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from helpers import GOLDEN, ROOT, SMALL_ARCH, golden_large_inputs, load_arch, rel_err, sample_idx
+from hipvae.lib import SEL_FRAME, SEL_TAP_WGRAD_W4, SEL_TN_W4
 from oracle import convvae_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def check(tag, got, want, tol, fails):
 ARCHS = {'vcc': load_arch(), 'small': SMALL_ARCH}
 
 
-FRAME_BIT = 1 << 21      # whole-frame-per-workgroup kernels for batches <= 512 (gfx950_frame.h); cleared = layered kernels
+FRAME_BIT = 1 << SEL_FRAME   # whole-frame-per-workgroup kernels for batches <= 512 (gfx950_frame.h); cleared = layered kernels
 
 
 def make_engine(which, impl, masks=(0xffffffff, 0xffffffff), precision=None, frame=False):
@@ -959,7 +960,7 @@ def test_hipgraph_replay_matches_eager():
 
 
 @pytest.mark.parametrize('F', [4096, 4099, 5000, 8209])
-@pytest.mark.parametrize('bit,entries,what', [(17, 1025 * 8, 'tap layer'), (16, 7 * 128 * 256, 'encoder layer 4')])
+@pytest.mark.parametrize('bit,entries,what', [(SEL_TAP_WGRAD_W4, 1025 * 8, 'tap layer'), (SEL_TN_W4, 7 * 128 * 256, 'encoder layer 4')])
 def test_weight_gradient_four_wave_kernels(F, bit, entries, what):
     """From 4 096 frames on the weight gradients of the 1025-tap layer and of encoder layer 4 run on four waves with
     128 x 128 wave tiles, operands by LDS-DMA into a ring of 16-row stages (k_toep_wgrad_bf16_w4, k_gemm_tn4); bits 17 / 16 of

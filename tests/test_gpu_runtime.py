@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from helpers import ROOT, load_arch, rel_err
+from hipvae.lib import SEL_FRAME
 from oracle import convvae_oracle as O
 from oracle import philox_ref
 
@@ -182,7 +183,7 @@ def test_backward_only_call_needs_a_matching_train_step():
             eng.train_bwd_target(xt, yt, et, xt, grads)
     eng.train_fwd_bwd(xt, yt, et, grads)
     eng.train_bwd_target(xt, yt, et, xt, grads)                        # ... and a fresh train step re-arms it
-    eng.set_tuned_masks(0xffffffff & ~(1 << 21), 0xffffffff & ~(1 << 21))
+    eng.set_tuned_masks(0xffffffff & ~(1 << SEL_FRAME), 0xffffffff & ~(1 << SEL_FRAME))
     with pytest.raises(L.HipVaeError, match='no matching train step'):
         eng.train_bwd_target(xt, yt, et, xt, grads)                    # another kernel family
 
@@ -197,7 +198,7 @@ def test_gradient_bucket_callback_ranges_and_order(path):
     arch = load_arch()
     eng = make_engine()
     if path == 'layered':
-        eng.set_tuned_masks(0xffffffff & ~(1 << 21), 0xffffffff & ~(1 << 21))
+        eng.set_tuned_masks(0xffffffff & ~(1 << SEL_FRAME), 0xffffffff & ~(1 << SEL_FRAME))
     eng.init_params(1)
     F = 64
     x, y, eps = O.make_inputs(arch, F, 1)

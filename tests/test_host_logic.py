@@ -444,3 +444,56 @@ def test_bench_site_groups_cover_every_tagged_launch_site():
     used = set(re.findall(r'VAENPVC_TIMED\("([a-z0-9_]+)"', src))
     small_batch = {t for t in used if t.startswith('frame_')}       # the small-batch frame kernels (not part of the layered step)
     assert used - small_batch <= set(flat), sorted(used - small_batch - set(flat))
+
+
+def _csrc_text():
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'vae-npvc_amd', 'csrc')
+    return {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith(('.hip', '.h', '.cpp'))}
+
+
+def test_selection_mask_bit_names_and_numbers_agree():
+    """The bits of the two kernel-selection masks have ONE list of names (include/vaenpvc_debug.h: vaenpvc_sel_bit) that
+    hipvae/lib.py mirrors as plain integers; the values other files spell as numbers (bench.py's 0xbfffffff, the fixtures'
+    masks) stay where they are, and no launch code names a bit by its number any more."""
+    import re
+    from hipvae import lib as L
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(ROOT, 'include', 'vaenpvc_debug.h')).read()
+    body = re.search(r'enum vaenpvc_sel_bit \{(.*?)\};', hdr, re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    enum = {n: int(v) for n, v in re.findall(r'VAENPVC_(SEL_[A-Z0-9_]+)\s*=\s*(\d+)', body)}
+    assert len(enum) == len([e for e in body.split(',') if e.strip()]), 'an enumerator without an explicit value'
+    mirror = {n: v for n, v in vars(L).items() if n.startswith('SEL_')}
+    assert enum == mirror, (sorted(set(enum.items()) ^ set(mirror.items())))
+    assert all(0 <= v < 32 for v in enum.values())
+    assert enum['SEL_FRAME'] == 21 and enum['SEL_WGRAD_STREAM'] == 30          # tests / bench.py: ~(1 << 21), 0xbfffffff
+    layers = ['SEL_ENC0', 'SEL_ENC1', 'SEL_ENC2', 'SEL_ENC3', 'SEL_ENC4', 'SEL_HEADS', 'SEL_MERGE',
+              'SEL_DEC0', 'SEL_DEC1', 'SEL_DEC2', 'SEL_DEC3']
+    assert [enum[n] for n in layers] == list(range(11))                          # the fixtures' 0x7ff
+    # two names may share a number only across the two masks (bit 30)
+    by_value = {}
+    for n, v in enum.items():
+        by_value.setdefault(v, []).append(n)
+    assert {v: sorted(ns) for v, ns in by_value.items() if len(ns) > 1} == {30: ['SEL_TOEP_MIN_FRAMES', 'SEL_WGRAD_STREAM']}
+    numbered = re.compile(r'\b(?:fwd_on|bwd_on)\(\s*\d|_mask\s*>>\s*\d')
+    left = ['%s: %s' % (fn, m.group(0)) for fn, text in _csrc_text().items() for m in numbered.finditer(text)]
+    assert not left, left
+
+
+def test_environment_switches_read_and_documented_agree():
+    """Every VAENPVC_* variable the library reads (a getenv in csrc/) has a row in the 'Environment switches' table of
+    scripts/README.md, and the table lists nothing the library no longer reads -- a switch cannot be added or dropped
+    without its documentation following."""
+    import re
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    read = set()
+    for text in _csrc_text().values():
+        read |= set(re.findall(r'getenv\(\s*"(VAENPVC_[A-Z0-9_]+)"\s*\)', text))
+        assert not re.search(r'getenv\(\s*[^"\s]', text), 'a getenv whose name is not a string literal cannot be checked'
+    readme = open(os.path.join(ROOT, 'scripts', 'README.md')).read()
+    section = re.search(r'^## Environment switches\n(.*?)(?=^## |\Z)', readme, re.S | re.M).group(1)
+    rows = [l for l in section.splitlines() if l.startswith('| `VAENPVC_')]
+    listed = [n for l in rows for n in re.findall(r'`(VAENPVC_[A-Z0-9_]+)`', l.split('|')[1])]
+    assert len(listed) == len(set(listed)), 'a switch has two rows'
+    assert set(listed) == read, (sorted(read - set(listed)), sorted(set(listed) - read))
+    assert len(read) >= 20

@@ -4,7 +4,7 @@
 //   frame_bwd    input-gradient chain of every frame with the LayerNorm backward in place
 //   frame_wgrad  every parameter gradient, one job-list launch (gfx950_frame_wgrad.h)
 //   frame_lnp    per-frame channel sums -> gradients of the LayerNorm parameters and conv biases (only behind the LAYERED
-//                weight gradients, backward-mask bit 20 cleared: the job list has its own segment for them)
+//                weight gradients, SEL_FRAME_WGRAD of the backward mask cleared: the job list has its own segment for them)
 //   toep_fwd / toep_bwd  train steps up to 128 frames: the 1025-tap layer between the two frame kernels (frame_split_on)
 // Reference: model/vae.py:72-137 (forward), trainer/vae.py:24 (autodiff).
 #include "gfx950_frame.h"
@@ -228,11 +228,11 @@ int64_t frame_lnp_floats(int64_t F) { return F * 3 * LNP_C; }
 
 bool frame_fwd_on(int64_t F) {
   const Runtime& r = rt();
-  return r.frame_max > 0 && F <= r.frame_max && ((r.fwd_mask >> 21) & 1u);
+  return r.frame_max > 0 && F <= r.frame_max && ((r.fwd_mask >> VAENPVC_SEL_FRAME) & 1u);
 }
 bool frame_bwd_on(int64_t F) {
   const Runtime& r = rt();
-  return r.frame_max > 0 && F <= r.frame_max && ((r.bwd_mask >> 21) & 1u);
+  return r.frame_max > 0 && F <= r.frame_max && ((r.bwd_mask >> VAENPVC_SEL_FRAME) & 1u);
 }
 
 void frame_pack(const Model& m, const float* P, const Ws& w, float* G, float* zero2, int nzero2, hipStream_t s, bool zero_only) {
@@ -242,14 +242,14 @@ void frame_pack(const Model& m, const float* P, const Ws& w, float* G, float* ze
                      G ? (int)m.n_params : 0, zero2, nzero2);
 }
 
-// Train steps run the 1025-tap layer outside the frame kernels (bit 18 of the backward mask, default set): needs the
+// Train steps run the 1025-tap layer outside the frame kernels (SEL_FRAME_SPLIT of the backward mask, default set): needs the
 // activated output of decoder layer 2 and the scratch both halves share
 // (up to FRAME_SPLIT_MAX frames: the frame kernels leave compute units idle there; at 256 frames every unit holds a frame
 //  and the 2 x 2048 extra workgroups cost more than the frame kernels save: 0.362 -> 0.378 ms, against 0.253 -> 0.229 ms at
 //  16 frames and 0.273 -> 0.254 at 64; VAENPVC_FRAME_SPLIT_MAX overrides)
 bool frame_split_on(const Ws& w, int64_t F) {
   static const int64_t fmax = getenv("VAENPVC_FRAME_SPLIT_MAX") ? atoll(getenv("VAENPVC_FRAME_SPLIT_MAX")) : 128;
-  return ((rt().bwd_mask >> 18) & 1u) && F <= fmax && w.dec_y && w.dy_tmp && w.frame_lnp && w.d_xh;
+  return ((rt().bwd_mask >> VAENPVC_SEL_FRAME_SPLIT) & 1u) && F <= fmax && w.dec_y && w.dy_tmp && w.frame_lnp && w.d_xh;
 }
 
 // mode: FM_* bits.  x may be null for decode-only, z_in null unless decode-only.

@@ -567,7 +567,7 @@ struct NtArgs {
   const float* rowbias;   // [nrb][ldrb] or nullptr: row idx[m] is added to output row m
   const int64_t* idx;
   int nrb, ldrb;
-  int lep;                // 1: result tile through LDS, 16-byte stores (set by the launcher: Runtime::nt_lep, env VAENPVC_NT_LEP)
+  int lep;                // 1: result tile through LDS, 16-byte stores (set by the launcher, always)
 };
 constexpr int NT_BM = 128, NT_BN = 128;
 constexpr int NT_MAXRB = 16;   // row-bias table rows the epilogue keeps in LDS (speakers; VCC2016: 10)
@@ -588,7 +588,7 @@ constexpr int nt_bk(int npl) { return npl >= 3 ? 32 : VAENPVC_NT_BK2; }
 // the result tile goes through LDS on its way out (round 5, EVERY plane count): [128][NT_EP_PITCH] floats behind the speaker table
 constexpr int NT_EP_PITCH = NT_BN + 4, NT_EP_OFF = NT_MAXRB * 128 * 4 + 128 * 4, NT_EP_LDS = NT_EP_OFF + NT_BM * NT_EP_PITCH * 4;   // 76 288 bytes
 // One plane INCLUDED on purpose: its 36 KB of staging alone would fit three workgroups per CU and the 76 KB tile leaves two, and the
-// tile still won the A/B (bf16 mode 4.46 -> 4.39 ms per step with VAENPVC_NT_LEP, DESIGN.md section 6 round 5: these sites are bound by
+// tile still won the A/B (bf16 mode 4.46 -> 4.39 ms per step, DESIGN.md section 6 round 5: these sites are bound by
 // their store instructions, not by the third workgroup).
 constexpr bool nt_lep(int npl) { return npl >= 1; }
 constexpr int nt_lds(int npl) {
@@ -866,7 +866,7 @@ inline void launch_gemm_nt_ar(const NtArgs& a, hipStream_t s);
 template <int NPL>
 inline void launch_gemm_nt(const NtArgs& a_, hipStream_t s) {
   NtArgs a = a_;
-  a.lep = rt().nt_lep ? 1 : 0;
+  a.lep = 1;
   if constexpr (NPL == 2) {   // (two planes: the result tile is parked in the B buffer, which one plane does not fill)
     if (rt().nt_ar && gemm_nt_ar_serves(a) && (rt().nt_ar > 1 || a.M / NT_BM >= 192)) {   // short K, many rows: the A-resident kernel (Runtime::nt_ar)
       launch_gemm_nt_ar<NPL>(a, s);
@@ -880,15 +880,7 @@ inline void launch_gemm_nt(const NtArgs& a_, hipStream_t s) {
       return;
     }
   }
-  const int ntiles = cdiv(a.M, NT_BM) * cdiv(a.N, NT_BN);
-  constexpr int SLOTS = 256 * VAENPVC_NT_WPS;     // resident workgroups of the chip
-  // (one plane: the one-tile kernel runs two workgroups per CU -- its LDS result tile, see nt_lep -- at 138 registers; the persistent form
-  //  needs 194 and was only measured with two planes and more: not used)
-  if (NPL >= 2 && rt().nt_persist > 0 && ntiles >= rt().nt_persist) {   // (Runtime::nt_persist, env VAENPVC_NT_PERSIST)
-    rt().ensure_lds(reinterpret_cast<const void*>(&k_gemm_nt<NPL, true>), nt_lds(NPL));
-    hipLaunchKernelGGL((k_gemm_nt<NPL, true>), dim3(SLOTS), dim3(256), nt_lds(NPL), s, a);
-    return;
-  }
+  const int ntiles = cdiv(a.M, NT_BM) * cdiv(a.N, NT_BN);   // one workgroup per tile (the persistent form measured slower: DESIGN.md section 6, round 5)
   rt().ensure_lds(reinterpret_cast<const void*>(&k_gemm_nt<NPL, false>), nt_lds(NPL));
   hipLaunchKernelGGL((k_gemm_nt<NPL, false>), dim3((unsigned)ntiles), dim3(256), nt_lds(NPL), s, a);
 }
@@ -1081,7 +1073,7 @@ struct TnpArgs {
   RowView av, bv;
   int lda, ldb;   // readable elements per row (loads are clamped to the row: ragged last column tile)
   int xcd;               // 1: XCD-aware tile order (the tiles of a row chunk on one XCD)
-  int tn4;               // 1: the four-wave kernel may be used (bit 16 of the backward mask)
+  int tn4;               // 1: the four-wave kernel may be used (VAENPVC_SEL_TN_W4 of the backward mask)
   int M, N, F, fchunk;   // F = number of reduction rows
   float* C;   // PLAIN: C[m*ldc + n] (n < split) ; ENC4: the TF kernel tensor [7][128][256] ; TRANS: C[n*ldc + m]
   float* C2;  // PLAIN: columns n >= split at n - split
@@ -1275,22 +1267,26 @@ template <int NPL, int EPI, int TI = 2, int TJ = 2>
 inline void launch_gemm_tn(TnpArgs a, int target_wgs, hipStream_t s) {
   if constexpr (NPL <= 2 && EPI != TN_EPI_TRANS && TI == 2 && TJ == 2) {
     // the four-wave kernel where a row chunk has many 256 x 256 tiles (encoder layer 4: 4 x 3) and the rows are plain
-    if (a.tn4 && a.F >= 4096 && a.av.R >= a.F && a.bv.R >= a.F && cdiv(a.M, 256) * cdiv(a.N, 256) >= rt().tn_w4_tiles)
+    if (a.tn4 && a.F >= 4096 && a.av.R >= a.F && a.bv.R >= a.F && cdiv(a.M, 256) * cdiv(a.N, 256) >= 8)
       return launch_gemm_tn4<NPL, EPI>(a, s);
   }
-  if constexpr (NPL <= 2) {
-    // measured (32 768 frames): one plane -27 % over six sites; two planes -17..24 % on the sites with few tiles per row
-    // chunk (merge, heads, encoder layer 3), equal on decoder layer 0, +10 % on encoder layer 4 (21 tiles: stays here)
-    const bool many_tiles = cdiv(a.M, 64 * TI) * cdiv(a.N, 128 * TJ) > 8;
-    if (!rt().tn_k16 && (NPL == 1 || !many_tiles)) return launch_gemm_tn32<NPL, EPI, TI, TJ, 2, 4>(a, target_wgs, s);
+  // the pipelined kernel, measured (32 768 frames): one plane -27 % over six sites; two planes -17..24 % on the sites with few tiles per
+  // row chunk (merge, heads, encoder layer 3), equal on decoder layer 0, +10 % on encoder layer 4 (21 tiles: stays here)
+  if constexpr (NPL == 1) {
+    return launch_gemm_tn32<NPL, EPI, TI, TJ, 2, 4>(a, target_wgs, s);
+  } else {
+    if constexpr (NPL == 2) {
+      const bool many_tiles = cdiv(a.M, 64 * TI) * cdiv(a.N, 128 * TJ) > 8;
+      if (!many_tiles) return launch_gemm_tn32<NPL, EPI, TI, TJ, 2, 4>(a, target_wgs, s);
+    }
+    using T = TnTile<NPL, TI, TJ>;
+    rt().ensure_lds(reinterpret_cast<const void*>(&k_gemm_tn<NPL, EPI, TI, TJ>), T::LDS);
+    const int tiles = cdiv(a.M, T::BM) * cdiv(a.N, T::BN);
+    const int zc = cmax(1, cmin_(cdiv(a.F, 64), cdiv(target_wgs, tiles)));
+    a.fchunk = rup(cdiv(a.F, zc), TP_KF);
+    dim3 grid((unsigned)(cdiv(a.M, T::BM) * cdiv(a.N, T::BN) * cdiv(a.F, a.fchunk)));
+    hipLaunchKernelGGL((k_gemm_tn<NPL, EPI, TI, TJ>), grid, dim3(512), T::LDS, s, a);
   }
-  using T = TnTile<NPL, TI, TJ>;
-  rt().ensure_lds(reinterpret_cast<const void*>(&k_gemm_tn<NPL, EPI, TI, TJ>), T::LDS);
-  const int tiles = cdiv(a.M, T::BM) * cdiv(a.N, T::BN);
-  const int zc = cmax(1, cmin_(cdiv(a.F, 64), cdiv(target_wgs, tiles)));
-  a.fchunk = rup(cdiv(a.F, zc), TP_KF);
-  dim3 grid((unsigned)(cdiv(a.M, T::BM) * cdiv(a.N, T::BN) * cdiv(a.F, a.fchunk)));
-  hipLaunchKernelGGL((k_gemm_tn<NPL, EPI, TI, TJ>), grid, dim3(512), T::LDS, s, a);
 }
 
 // ---------------------------------------------------------------- C += A^T B, pipelined (up to two planes)

@@ -296,7 +296,7 @@ template <int NPL>
 static void cv_gemm(int site, const float* wplanes, const float* xplanes, float* out, const float* bias, int F, hipStream_t s) {
   const CgArgs a = cv_gemm_args(site, wplanes, xplanes, out, bias, F);
   if constexpr (NPL <= 2) {
-    if (rt().cg_pf && cgemm_pf_serves(a)) {   // encoder layer 3's input gradient: the tile that owns whole frames (VAENPVC_CG_PF=0: A/B)
+    if (cgemm_pf_serves(a)) {   // encoder layer 3's input gradient: the tile that owns whole frames
       launch_cgemm_pf<NPL>(a, s);
       return;
     }
@@ -363,10 +363,10 @@ static void cv_wgrad(int site, const float* aplanes, const float* bplanes, float
   t.F = F * v.R;
   t.C = dW;
   t.ldc = v.M;
-  t.xcd = rt().tn_xcd >= 0 ? rt().tn_xcd : (v.M > 64 ? 1 : 0);   // measured: pays with >= 2 tiles of 128 x 256 per row chunk
+  t.xcd = v.M > 64 ? 1 : 0;   // measured: pays with >= 2 tiles of 128 x 256 per row chunk
   if constexpr (NPL <= 2) {
-    // decoder layer 0 (M = 81, N = 288): the 96 x 288 tile of the 3 x 3 wave grid instead of two 128 x 256 tiles (VAENPVC_TN_D0FIT=0: A/B)
-    if (site == CW_D0 && rt().tn_d0fit && !rt().tn_k16) return launch_gemm_tn32<NPL, TN_EPI_TRANS, 1, 3, 3, 3>(t, target_wgs, s);
+    // decoder layer 0 (M = 81, N = 288): the 96 x 288 tile of the 3 x 3 wave grid instead of two 128 x 256 tiles (36 % of their MFMA work useful)
+    if (site == CW_D0) return launch_gemm_tn32<NPL, TN_EPI_TRANS, 1, 3, 3, 3>(t, target_wgs, s);
   }
   if (v.M > 64) launch_gemm_tn<NPL, TN_EPI_TRANS, 2, 2>(t, target_wgs, s);
   else if (t.N > 128) launch_gemm_tn<NPL, TN_EPI_TRANS, 1, 2>(t, target_wgs, s);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/vaenpvc_debug.h"   // vaenpvc_sel_bit: names of the selection-mask bits
 #include "model.h"
 #include "philox.h"
 #include "runtime.h"

@@ -16,6 +16,36 @@ PREC_BF16X3, PREC_BF16X2, PREC_BF16 = 3, 2, 1
 # bf16 terms per fp32 operand on the bf16 matrix cores: 'bf16x2' (default, alias 'auto'): 16 mantissa bits per operand;
 # 'bf16x3': fp32-exact; 'bf16': plain bf16 operands (the bf16 mode)
 PRECISIONS = {'auto': 2, 'bf16x2': 2, 'bf16x3': 3, 'bf16': 1}
+# bits of the two kernel-selection masks (Engine.set_tuned_masks): the names of include/vaenpvc_debug.h, vaenpvc_sel_bit
+SEL_ENC0 = 0
+SEL_ENC1 = 1
+SEL_ENC2 = 2
+SEL_ENC3 = 3
+SEL_ENC4 = 4
+SEL_HEADS = 5
+SEL_MERGE = 6
+SEL_DEC0 = 7
+SEL_DEC1 = 8
+SEL_DEC2 = 9
+SEL_DEC3 = 10
+SEL_FBWD_MIN_FRAMES = 14
+SEL_FBWD = 15
+SEL_TN_W4 = 16
+SEL_TAP_WGRAD_W4 = 17
+SEL_FRAME_SPLIT = 18
+SEL_ENC0_FUSED_BWD = 19
+SEL_FRAME_WGRAD = 20
+SEL_FRAME = 21
+SEL_FCONV_R_MIN_FRAMES = 22
+SEL_ENC0_WAVE_MIN_FRAMES = 23
+SEL_FWGRAD_MIN_FRAMES = 24
+SEL_FCONV_MIN_FRAMES = 25
+SEL_CV_SITE_SET = 26
+SEL_VIEW_GEMM = 27
+SEL_PLANE_GEMM_MIN_FRAMES = 28
+SEL_PLANE_GEMM = 29
+SEL_TOEP_MIN_FRAMES = 30
+SEL_WGRAD_STREAM = 30
 
 
 class HipVaeError(RuntimeError):
