@@ -406,6 +406,52 @@ int vaenpvc_mcd_dtw(const float* d_spA, const float* d_enA, const float* d_f0A, 
                     int32_t n_pair, int64_t cells, const double* d_W, int32_t order, double* d_results,
                     int32_t* d_path, double* d_D, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Training-set statistics on the device (build.py --device; the host path of build.py is NumPy).  Both entries enqueue
+ * on `stream`, allocate nothing, do not synchronise with the host and use no floating-point atomic (integer histogram
+ * adds only): a call returns the same bytes every time.  DESIGN.md section 17; restated by tests/stats_ref.py.
+ *
+ * vaenpvc_column_select: exact per-column order statistics.  d_x is a float32 matrix of F rows and H columns with a row
+ * stride of ld floats (ld >= H; a raw record buffer [F, 1029] is used in place with ld = 1029).  host_ranks: HOST array
+ * of n_rank (1 .. VAENPVC_SELECT_MAX_RANKS) zero-based ranks in [0, F), in any order, duplicates allowed.
+ * d_out[r * H + h] = np.sort(x[:, h])[host_ranks[r]]: an element of the column, no interpolation (-0.0 sorts just below
+ * +0.0).  d_flag: device int32[1]; the call stores 0, then sets bit 0 if any element of the F x H window is NaN or
+ * +-Inf; the outputs of such a column are then unspecified (every write stays in bounds).  Checked (VAENPVC_E_ARG): no
+ * NULL pointer, 1 <= F <= 2^31 - 1 (an empty column has no order statistic), 1 <= H <= 2^21, H <= ld <= 2^24, n_rank
+ * and every rank in range.  d_ws: >= vaenpvc_column_select_workspace_bytes(F, H, n_rank) bytes (VAENPVC_E_WORKSPACE if
+ * shorter or NULL), 16-byte aligned.  Its layout, every region starting at a 256-byte boundary in this order:
+ *   hist    uint32 [n_rank, H, 256]   digit counts of the current radix pass per (slot, column); zero on return
+ *   prefix  uint32 [n_rank, H]        the selected element's order-preserving key (negative floats: every bit flipped,
+ *                                     the others: the sign bit flipped)
+ *   krem    uint32 [n_rank, H]        the rank among the elements that equal the selected one (0 .. ties - 1)
+ *   lead    int32  [n_rank, H]        the lowest rank index that selected the same element in this column
+ * The select reads d_x once for the first 8 key bits and once per further 8 bits and distinct prefix still alive:
+ * between 4 and 1 + 3 n_rank passes.
+ *
+ * vaenpvc_speaker_stats: utterance u is rows d_offsets[u] .. d_offsets[u+1] (device int64 [n_seg+1], non-decreasing,
+ * [0] = 0, [n_seg] = F) of d_sp (float32, F x H, row stride ld_sp >= H floats) and of d_f0 (float32, element stride
+ * ld_f0 >= 1 floats); d_spk[u] (device int32 [n_seg]) is its speaker in [0, n_spk).  Neither array is checked here --
+ * the binding does that; on the device offsets are clamped to [0, F] and an id outside [0, n_spk) belongs to no speaker,
+ * so nothing is read or written out of bounds.  All arithmetic is float64, in orders that depend only on the lengths of
+ * the speaker's utterances and their order:
+ *   d_lf0   double [n_spk, 3]   (count, mean, population std) of ln f0 over the speaker's frames with f0 > 2 (strict);
+ *                               count == 0: mean = std = NaN
+ *   d_gv    double [n_spk, H]   per bin, the mean over the speaker's utterances of >= 2 frames of the utterance's
+ *                               biased variance of sp (two passes); NaN where d_n_utt is 0
+ *   d_n_utt int64  [n_spk]      the number of those utterances
+ * A speaker's results are the same bytes wherever its utterances stand among the others'.  Checked (VAENPVC_E_ARG): no
+ * NULL pointer, F >= 0, n_seg >= 1, n_spk >= 1, 1 <= H <= 2^21, H <= ld_sp <= 2^24, 1 <= ld_f0 <= 2^24.  d_ws: >=
+ * vaenpvc_speaker_stats_workspace_bytes(F, n_seg, H) bytes (VAENPVC_E_WORKSPACE if shorter or NULL), 16-byte aligned:
+ *   uvar    double [n_seg, H]   the utterance variances (rows of utterances under 2 frames are not written)
+ *   ustat   double [n_seg, 3]   (count, mean, M2) of ln f0 per utterance */
+#define VAENPVC_SELECT_MAX_RANKS 8
+int64_t vaenpvc_column_select_workspace_bytes(int64_t F, int32_t H, int32_t n_rank);
+int vaenpvc_column_select(const float* d_x, int64_t F, int32_t H, int64_t ld, const int64_t* host_ranks, int32_t n_rank,
+                          float* d_out, int32_t* d_flag, void* d_ws, size_t ws_bytes, void* stream);
+int64_t vaenpvc_speaker_stats_workspace_bytes(int64_t F, int32_t n_seg, int32_t H);
+int vaenpvc_speaker_stats(const float* d_sp, int64_t ld_sp, const float* d_f0, int64_t ld_f0, const int64_t* d_offsets,
+                          const int32_t* d_spk, int32_t n_seg, int32_t n_spk, int64_t F, int32_t H, double* d_lf0,
+                          double* d_gv, int64_t* d_n_utt, void* d_ws, size_t ws_bytes, void* stream);
+
 /* analyzer.read record slicing (analyzer.py:113-127): rows of `rec_floats` float32
  * (1029) -> x = Tanhize(row[0:H]) and y = int64(row[rec_floats-1]) (bit-exact cast). */
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H,

@@ -499,6 +499,64 @@ int vaenpvc_gv_postfilter(const float* d_x, const int64_t* d_offsets, int32_t n_
   return check_launch("gv_postfilter");
 }
 
+static int select_shape_check(int64_t F, int32_t H, int32_t n_rank) {
+  if (F < 1 || F > INT32_MAX) return fail(VAENPVC_E_ARG, "F must be in [1, 2^31 - 1] (got %lld)", (long long)F);
+  if (H < 1 || H > SEL_MAX_H) return fail(VAENPVC_E_ARG, "H must be in [1, %d] (got %d)", SEL_MAX_H, H);
+  if (n_rank < 1 || n_rank > VAENPVC_SELECT_MAX_RANKS)
+    return fail(VAENPVC_E_ARG, "n_rank must be in [1, %d] (got %d)", VAENPVC_SELECT_MAX_RANKS, n_rank);
+  return 0;
+}
+
+int64_t vaenpvc_column_select_workspace_bytes(int64_t F, int32_t H, int32_t n_rank) {
+  if (select_shape_check(F, H, n_rank) != 0) return VAENPVC_E_ARG;
+  return column_select_workspace_bytes(H, n_rank);
+}
+
+int vaenpvc_column_select(const float* d_x, int64_t F, int32_t H, int64_t ld, const int64_t* host_ranks, int32_t n_rank,
+                          float* d_out, int32_t* d_flag, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_x || !host_ranks || !d_out || !d_flag) return fail(VAENPVC_E_ARG, "null argument");
+  if (select_shape_check(F, H, n_rank) != 0) return VAENPVC_E_ARG;
+  if (ld < H || ld > SEL_MAX_LD)
+    return fail(VAENPVC_E_ARG, "ld must be in [H, %lld] (got %lld, H %d)", (long long)SEL_MAX_LD, (long long)ld, H);
+  for (int r = 0; r < n_rank; ++r)
+    if (host_ranks[r] < 0 || host_ranks[r] >= F)
+      return fail(VAENPVC_E_ARG, "rank %d is %lld, outside [0, %lld)", r, (long long)host_ranks[r], (long long)F);
+  const int64_t need = column_select_workspace_bytes(H, n_rank);
+  if (d_ws == nullptr || ws_bytes < (size_t)need)
+    return fail(VAENPVC_E_WORKSPACE, "workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+  if (((uintptr_t)d_ws & 15) != 0) return fail(VAENPVC_E_ARG, "workspace must be 16-byte aligned");
+  launch_column_select(d_x, F, H, ld, host_ranks, n_rank, d_out, d_flag, d_ws, (hipStream_t)stream);
+  return check_launch("column_select");
+}
+
+static int speaker_stats_shape_check(int64_t F, int32_t n_seg, int32_t H) {
+  if (F < 0 || n_seg < 1 || H < 1 || H > SEL_MAX_H)
+    return fail(VAENPVC_E_ARG, "bad argument (F %lld, n_seg %d, H %d)", (long long)F, n_seg, H);
+  return 0;
+}
+
+int64_t vaenpvc_speaker_stats_workspace_bytes(int64_t F, int32_t n_seg, int32_t H) {
+  if (speaker_stats_shape_check(F, n_seg, H) != 0) return VAENPVC_E_ARG;
+  return speaker_stats_workspace_bytes(n_seg, H);
+}
+
+int vaenpvc_speaker_stats(const float* d_sp, int64_t ld_sp, const float* d_f0, int64_t ld_f0, const int64_t* d_offsets,
+                          const int32_t* d_spk, int32_t n_seg, int32_t n_spk, int64_t F, int32_t H, double* d_lf0,
+                          double* d_gv, int64_t* d_n_utt, void* d_ws, size_t ws_bytes, void* stream) {
+  if (!d_sp || !d_f0 || !d_offsets || !d_spk || !d_lf0 || !d_gv || !d_n_utt) return fail(VAENPVC_E_ARG, "null argument");
+  if (speaker_stats_shape_check(F, n_seg, H) != 0) return VAENPVC_E_ARG;
+  if (n_spk < 1 || ld_sp < H || ld_f0 < 1 || ld_sp > SEL_MAX_LD || ld_f0 > SEL_MAX_LD)
+    return fail(VAENPVC_E_ARG, "bad argument (n_spk %d, ld_sp %lld, ld_f0 %lld, H %d)", n_spk, (long long)ld_sp,
+                (long long)ld_f0, H);
+  const int64_t need = speaker_stats_workspace_bytes(n_seg, H);
+  if (d_ws == nullptr || ws_bytes < (size_t)need)
+    return fail(VAENPVC_E_WORKSPACE, "workspace too small: need %lld bytes, got %lld", (long long)need, (long long)ws_bytes);
+  if (((uintptr_t)d_ws & 15) != 0) return fail(VAENPVC_E_ARG, "workspace must be 16-byte aligned");
+  launch_speaker_stats(d_sp, ld_sp, d_f0, ld_f0, d_offsets, d_spk, n_seg, n_spk, F, H, d_lf0, d_gv, d_n_utt, d_ws,
+                       (hipStream_t)stream);
+  return check_launch("speaker_stats");
+}
+
 static bool synth_shape_ok(int32_t n_seg, int64_t S, int32_t H, int32_t fs) {
   // pulse samples and slot counts fit int32, launch grids 32 bits
   return n_seg > 0 && n_seg < (1 << 24) && S >= 0 && S <= INT32_MAX && H == 513 && fs >= 8000 && fs <= 48000;

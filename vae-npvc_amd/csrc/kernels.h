@@ -152,6 +152,18 @@ void launch_mcd_dtw(const float* spA, const float* enA, const float* f0A, const 
                     int64_t cells, const double* W, int order, double* results, int32_t* path, double* D, void* ws,
                     hipStream_t s);
 
+// ---- training-set statistics of build.py --device (gfx950_stats.hip) ----
+constexpr int SEL_MAX_RANKS = 8;        // = VAENPVC_SELECT_MAX_RANKS
+constexpr int64_t SEL_MAX_LD = 1 << 24;  // row stride in floats: the histogram kernel's in-slice offsets stay 32-bit
+constexpr int SEL_MAX_H = 1 << 21;      // 64-column groups fit the grid's y dimension
+int64_t column_select_workspace_bytes(int H, int n_rank);
+void launch_column_select(const float* x, int64_t F, int H, int64_t ld, const int64_t* ranks, int n_rank, float* out,
+                          int32_t* flag, void* ws, hipStream_t s);
+int64_t speaker_stats_workspace_bytes(int n_seg, int H);
+void launch_speaker_stats(const float* sp, int64_t ld_sp, const float* f0, int64_t ld_f0, const int64_t* off,
+                          const int32_t* spk, int n_seg, int n_spk, int64_t F, int H, double* lf0, double* gv,
+                          int64_t* n_utt, void* ws, hipStream_t s);
+
 // ---- tuned gfx950 kernels for the VCC2016 geometry (gfx950_*.hip) ----------------
 namespace tuned {
 // step masks: bit set = use the tuned kernel for that step, clear = generic kernel.
