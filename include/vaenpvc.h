@@ -452,6 +452,46 @@ int vaenpvc_speaker_stats(const float* d_sp, int64_t ld_sp, const float* d_f0, i
                           const int32_t* d_spk, int32_t n_seg, int32_t n_spk, int64_t F, int32_t H, double* d_lf0,
                           double* d_gv, int64_t* d_n_utt, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Band-limited resampling of the data path (analyzer.py --resample; the reference's analyzer.py:40 reads every wav with
+ * librosa.load(sr=16000), which resamples; librosa is a CPU library this project does not have).  The definition is
+ * DESIGN.md section 18, restated by tests/resample_ref.py; the constants are the ones resampy documents for its
+ * `kaiser_best` filter, sample-level equality with librosa is not claimed.  Rates rate_in -> rate_out in Hz, g their gcd,
+ * L = rate_out / g, M = rate_in / g, s = min(1, L / M), K = ceil(64 / s).  With the prototype, in input-sample time t,
+ *   h(t) = s R sinc(s R t) I0(B sqrt(1 - v^2)) / I0(B),  v = s t / 64,  h = 0 where |v| >= 1,
+ *   R = 0.9475937167399596, B = 14.769656459379492, sinc the normalised sinc,
+ * a segment of n input samples gives (n L + M - 1) / M (integer division) output samples; output m of the segment sits
+ * at u = m M / L input samples and is  y[m] = sum_{j = -K+1 .. K} x[floor(u) + j] h(frac(u) - j),  x zero outside the
+ * segment, summed in float64 in ascending j and rounded once to float32.  frac(u) depends only on r = m mod L: the
+ * weights are the table T, double [2K][L] row-major, T[j + K - 1][r] = h(((r M) mod L) / L - j).
+ *
+ * vaenpvc_resample_plan (host only, no device work): *up = L, *down = M, *half_taps = K.  VAENPVC_E_ARG unless
+ * 1000 <= rate_in, rate_out <= 384000, rate_in != rate_out, no NULL pointer, the table has at most
+ * VAENPVC_RESAMPLE_MAX_TABLE entries (2 K L <= 2^24) and a workgroup can stage the input window of one tile:
+ * ceil(VAENPVC_RESAMPLE_TILE M / L) + 2 K <= VAENPVC_RESAMPLE_MAX_WINDOW samples.  (8000, 11025, 22050, 24000, 32000,
+ * 44100, 48000 and 96000 -> 16000 are all inside.)
+ *
+ * vaenpvc_resample_filter (host only, no device work): fills host_table, double [2K][L], in float64; the only place the
+ * weights are computed.  VAENPVC_E_ARG as for the plan, or when host_table is NULL.  The caller uploads it.
+ *
+ * vaenpvc_resample: n_seg segments back to back: segment u is samples d_in_offsets[u] .. [u+1] of d_x [S_in] (float32)
+ * and outputs d_out_offsets[u] .. [u+1] of d_y [S_out] (float32), (n_u L + M - 1) / M of them.  Both offset arrays are
+ * device int64 [n_seg+1], non-decreasing, [0] = 0, [n_seg] = S_in resp. S_out, every n_u >= 1; NOT checked here -- the
+ * binding checks them on the host (on the device offsets are clamped to [0, S_in] resp. [0, S_out]: a malformed array
+ * cannot make the kernel read or write out of bounds).  d_table: the device copy of T for this rate pair.  A segment's
+ * outputs depend only on its own samples (bit for bit, whatever its offset or neighbours in the batch).  One workgroup
+ * handles VAENPVC_RESAMPLE_TILE consecutive outputs of one segment.  Checked (VAENPVC_E_ARG): the plan's conditions, no
+ * NULL pointer, 1 <= n_seg < 2^24, n_seg <= S_in <= INT32_MAX, n_seg <= S_out <= min(INT32_MAX,
+ * (S_in L + M - 1) / M + n_seg), no overlap of d_y with d_x, d_table or an offset array.  No workspace: the call enqueues
+ * one kernel on `stream`, allocates nothing, does not synchronise with the host and uses no atomic. */
+#define VAENPVC_RESAMPLE_TILE 256
+#define VAENPVC_RESAMPLE_MAX_TABLE (1 << 24)
+#define VAENPVC_RESAMPLE_MAX_WINDOW 8192
+int vaenpvc_resample_plan(int32_t rate_in, int32_t rate_out, int32_t* up, int32_t* down, int32_t* half_taps);
+int vaenpvc_resample_filter(int32_t rate_in, int32_t rate_out, double* host_table);
+int vaenpvc_resample(const float* d_x, const int64_t* d_in_offsets, const int64_t* d_out_offsets, int32_t n_seg,
+                     int64_t S_in, int64_t S_out, int32_t rate_in, int32_t rate_out, const double* d_table, float* d_y,
+                     void* stream);
+
 /* analyzer.read record slicing (analyzer.py:113-127): rows of `rec_floats` float32
  * (1029) -> x = Tanhize(row[0:H]) and y = int64(row[rec_floats-1]) (bit-exact cast). */
 int vaenpvc_unpack_records(const float* d_records, int64_t F, int32_t rec_floats, int32_t H,

@@ -10,7 +10,8 @@ min_after_dequeue semantics.
 Feature extraction (analyzer.py:25-72,189-193) runs on the device: `extract` / `extract_and_save_bin_to` read 16-bit
 PCM wavs with the standard `wave` module and hand them to `hipvae.world.analyze` (vaenpvc_analyze, WORLD-style
 DIO -> StoneMask -> CheapTrick -> D4C); `--batch_seconds` groups consecutive files into one device
-call.  Synthesis is convert.py --vocoder device.
+call; with `--resample` wavs of other rates are brought to 16 kHz on the device first (`hipvae.resample`, vaenpvc_resample,
+DESIGN.md section 18).  Synthesis is convert.py --vocoder device.
 """
 import argparse
 import glob
@@ -329,19 +330,58 @@ def read_whole_features(file_pattern, num_epochs=1):
             }
 
 
-def read_wav(path, fs=16000):
-    """librosa.load(path, sr=fs, mono=True) for 16-bit integer PCM at `fs`: int16 / 32768, channels averaged.
-    Other sample widths and rates raise ValueError (resampling is out of scope)."""
+def read_wav_native(path):
+    """librosa.load(path, sr=None, mono=True) for 16-bit integer PCM: (int16 / 32768 with the channels averaged, the
+    file's own rate).  Other sample widths raise ValueError."""
     with wave.open(path, 'rb') as w:
         nch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
         raw = w.readframes(n)
     if width != 2:
         raise ValueError('%s: %d-bit samples; only 16-bit integer PCM is supported' % (path, 8 * width))
-    if rate != fs:
-        raise ValueError('%s: sampled at %d Hz, expected %d Hz (resample first)' % (path, rate, fs))
     x = np.frombuffer(raw, '<i2').astype(np.float64) / 32768.0
     x = x.reshape(-1, nch).mean(axis=1)
-    return x.astype(np.float32)
+    return x.astype(np.float32), rate
+
+
+def read_wav(path, fs=16000):
+    """librosa.load(path, sr=fs, mono=True) for 16-bit integer PCM at `fs`: int16 / 32768, channels averaged.
+    Other sample widths and rates raise ValueError (read_wav_native + resample_group take other rates)."""
+    x, rate = read_wav_native(path)
+    if rate != fs:
+        raise ValueError('%s: sampled at %d Hz, expected %d Hz (resample first)' % (path, rate, fs))
+    return x
+
+
+def resample_group(xs, rate_in, fs):
+    """Device resampling of the waveforms xs from rate_in to fs (one call, hipvae.resample) -> float32 arrays."""
+    from hipvae import resample as RS
+    dev = torch.device('cuda', torch.cuda.current_device())
+    x = torch.from_numpy(np.concatenate(xs).astype(np.float32)).to(dev)
+    y, outs = RS.resample(x, [len(v) for v in xs], rate_in, fs)
+    y = y.cpu().numpy()
+    out, o = [], 0
+    for n in outs:
+        out.append(y[o:o + n])
+        o += n
+    return out
+
+
+def resample_runs(xs, rates, fs, batch_seconds):
+    """The waveforms xs (xs[i] sampled at rates[i]) at `fs`, in order: a file already at fs is passed through untouched;
+    consecutive files of one other rate are gathered into runs of at most batch_seconds of input audio and resampled,
+    one resample_group call per run."""
+    out = list(xs)
+    i = 0
+    while i < len(xs):
+        j = i + 1
+        while j < len(xs) and rates[j] == rates[i]:
+            j += 1
+        if rates[i] != fs:
+            for run in group_by_seconds([(k, len(xs[k])) for k in range(i, j)], batch_seconds, rates[i]):
+                for k, y in zip(run, resample_group([xs[k] for k in run], rates[i], fs)):
+                    out[k] = y
+        i = j
+    return out
 
 
 def _analyze(xs, fs, f0_ceil):
@@ -358,9 +398,13 @@ def _analyze(xs, fs, f0_ceil):
     return out
 
 
-def extract(filename, fs=16000, f0_ceil=500.0):
-    """analyzer.py:35-47: one wav -> [T, 1028] float32 rows [sp (log10, energy-normalised), ap, f0, en]."""
-    return _analyze([read_wav(filename, fs)], fs, f0_ceil)[0]
+def extract(filename, fs=16000, f0_ceil=500.0, resample=False):
+    """analyzer.py:35-47: one wav -> [T, 1028] float32 rows [sp (log10, energy-normalised), ap, f0, en].  With
+    resample=True a wav of another rate is resampled to fs on the device first."""
+    if not resample:
+        return _analyze([read_wav(filename, fs)], fs, f0_ceil)[0]
+    x, rate = read_wav_native(filename)
+    return _analyze(resample_runs([x], [rate], fs, 0.0), fs, f0_ceil)[0]
 
 
 def list_wavs(dir_to_wav):
@@ -396,14 +440,26 @@ def group_by_seconds(items, seconds, fs=16000):
     return groups
 
 
-def extract_and_save_bin_to(dir_to_bin, dir_to_wav, fs=16000, f0_ceil=500.0, batch_seconds=60.0):
+def extract_and_save_bin_to(dir_to_bin, dir_to_wav, fs=16000, f0_ceil=500.0, batch_seconds=60.0, resample=False):
     """analyzer.py:50-72: <dir_to_bin>/<set>/<speaker>/<basename>.bin for every wav, records [sp, ap, f0, en, speaker]
-    written by write_bin.  Returns the written paths."""
+    written by write_bin.  Returns the written paths.  With resample=True the wavs are read at their own rate and those
+    of another rate than fs are resampled on the device (resample_runs) ahead of the analysis."""
     todo = []
-    for d, s, path in list_wavs(dir_to_wav):
-        print(path)
-        x = read_wav(path, fs)
-        todo.append(((d, s, path, x), len(x)))
+    if resample:
+        found, xs, rates = [], [], []
+        for d, s, path in list_wavs(dir_to_wav):
+            print(path)
+            x, rate = read_wav_native(path)
+            found.append((d, s, path))
+            xs.append(x)
+            rates.append(rate)
+        for (d, s, path), x in zip(found, resample_runs(xs, rates, fs, batch_seconds)):
+            todo.append(((d, s, path, x), len(x)))
+    else:
+        for d, s, path in list_wavs(dir_to_wav):
+            print(path)
+            x = read_wav(path, fs)
+            todo.append(((d, s, path, x), len(x)))
     written = []
     for group in group_by_seconds(todo, batch_seconds, fs):
         feats = _analyze([g[3] for g in group], fs, f0_ceil)
@@ -419,16 +475,21 @@ def main(argv=None):
     p = argparse.ArgumentParser(description='WORLD-style analysis of <set>/<speaker>/*.wav into .bin records')
     p.add_argument('--dir_to_wav', default='./dataset/vcc2016/wav', help='Dir to *.wav')
     p.add_argument('--dir_to_bin', default='./dataset/vcc2016/bin', help='Dir to output *.bin')
-    p.add_argument('--fs', type=int, default=16000, help='Global sampling frequency (only 16000)')
+    p.add_argument('--fs', type=int, default=16000,
+                   help='Global sampling frequency of the analysis (only 16000; see --resample for wavs of other rates)')
     p.add_argument('--f0_ceil', type=float, default=500.0, help='Global f0 ceiling')
     p.add_argument('--batch_seconds', type=float, default=60.0,
                    help='seconds of audio per device call (consecutive files; <= 0: one file per call)')
+    p.add_argument('--resample', action='store_true', help='resample wavs of other rates to --fs on the device')
     a = p.parse_args(argv)
     if a.fs != 16000:
-        p.error('--fs must be 16000 (resampling is out of scope)')
+        p.error('--fs must be 16000 (the analysis and synthesis rate; --resample brings wavs of other rates to it)')
     if not 71.0 < a.f0_ceil <= 800.0:
         p.error('--f0_ceil must be in (71, 800]')
-    extract_and_save_bin_to(a.dir_to_bin, a.dir_to_wav, a.fs, a.f0_ceil, a.batch_seconds)
+    if a.resample:
+        extract_and_save_bin_to(a.dir_to_bin, a.dir_to_wav, a.fs, a.f0_ceil, a.batch_seconds, resample=True)
+    else:
+        extract_and_save_bin_to(a.dir_to_bin, a.dir_to_wav, a.fs, a.f0_ceil, a.batch_seconds)
 
 
 if __name__ == '__main__':

@@ -665,6 +665,47 @@ int vaenpvc_mcep_matrix(int32_t order, double alpha, int32_t H, double* host_W) 
   return 0;
 }
 
+int vaenpvc_resample_plan(int32_t rate_in, int32_t rate_out, int32_t* up, int32_t* down, int32_t* half_taps) {
+  if (!up || !down || !half_taps) return fail(VAENPVC_E_ARG, "null argument");
+  int L, M, K;
+  if (!resample_plan_host(rate_in, rate_out, &L, &M, &K))
+    return fail(VAENPVC_E_ARG,
+                "cannot resample %d -> %d Hz: need distinct rates in [1000, 384000], 2K L <= %d table entries and a "
+                "window ceil(%d M / L) + 2K <= %d samples",
+                rate_in, rate_out, VAENPVC_RESAMPLE_MAX_TABLE, VAENPVC_RESAMPLE_TILE, VAENPVC_RESAMPLE_MAX_WINDOW);
+  *up = L;
+  *down = M;
+  *half_taps = K;
+  return 0;
+}
+
+int vaenpvc_resample_filter(int32_t rate_in, int32_t rate_out, double* host_table) {
+  if (!host_table) return fail(VAENPVC_E_ARG, "null argument");
+  int32_t L, M, K;
+  if (vaenpvc_resample_plan(rate_in, rate_out, &L, &M, &K) != 0) return VAENPVC_E_ARG;
+  resample_filter_host(L, M, K, host_table);
+  return 0;
+}
+
+int vaenpvc_resample(const float* d_x, const int64_t* d_in_offsets, const int64_t* d_out_offsets, int32_t n_seg,
+                     int64_t S_in, int64_t S_out, int32_t rate_in, int32_t rate_out, const double* d_table, float* d_y,
+                     void* stream) {
+  if (!d_x || !d_in_offsets || !d_out_offsets || !d_table || !d_y) return fail(VAENPVC_E_ARG, "null argument");
+  int32_t L, M, K;
+  if (vaenpvc_resample_plan(rate_in, rate_out, &L, &M, &K) != 0) return VAENPVC_E_ARG;
+  // every segment has >= 1 sample and so >= 1 output; S_out is at most what the samples allow (one ceil per segment)
+  if (n_seg < 1 || n_seg >= (1 << 24) || S_in < n_seg || S_in > INT32_MAX || S_out < n_seg || S_out > INT32_MAX ||
+      S_out > (S_in * L + M - 1) / M + n_seg)
+    return fail(VAENPVC_E_ARG, "bad argument (n_seg %d, S_in %lld, S_out %lld, %d -> %d Hz)", n_seg, (long long)S_in,
+                (long long)S_out, rate_in, rate_out);
+  const int64_t ny = S_out * 4, no = ((int64_t)n_seg + 1) * 8;
+  if (overlaps(d_y, ny, d_x, S_in * 4) || overlaps(d_y, ny, d_table, (int64_t)2 * K * L * 8) ||
+      overlaps(d_y, ny, d_in_offsets, no) || overlaps(d_y, ny, d_out_offsets, no))
+    return fail(VAENPVC_E_ARG, "d_y must not overlap an input");
+  launch_resample(d_x, d_in_offsets, d_out_offsets, n_seg, S_in, S_out, L, M, K, d_table, d_y, (hipStream_t)stream);
+  return check_launch("resample");
+}
+
 static bool mcd_shape_ok(int32_t n_pair, int64_t Fa, int64_t Fb, int64_t cells, int32_t order) {
   // every utterance has 1 .. VAENPVC_MCD_MAX_FRAMES frames, so cells (the sum of Ta * Tb) lies between the larger side's
   // frame count and n_pair * MAX^2; the offsets themselves are device data (checked by the binding and by k_mcd_prep)

@@ -164,6 +164,14 @@ void launch_speaker_stats(const float* sp, int64_t ld_sp, const float* f0, int64
                           const int32_t* spk, int n_seg, int n_spk, int64_t F, int H, double* lf0, double* gv,
                           int64_t* n_utt, void* ws, hipStream_t s);
 
+// ---- band-limited resampling of analyzer.py --resample (gfx950_resample.hip) ----
+// host only: L = rate_out / gcd, M = rate_in / gcd, K = ceil(64 / min(1, L / M)); false when the pair is outside the
+// limits of include/vaenpvc.h
+bool resample_plan_host(int rate_in, int rate_out, int* up, int* down, int* half_taps);
+void resample_filter_host(int L, int M, int K, double* T);      // host only: T [2K][L]
+void launch_resample(const float* x, const int64_t* ioff, const int64_t* ooff, int n_seg, int64_t S_in, int64_t S_out,
+                     int L, int M, int K, const double* T, float* y, hipStream_t s);
+
 // ---- tuned gfx950 kernels for the VCC2016 geometry (gfx950_*.hip) ----------------
 namespace tuned {
 // step masks: bit set = use the tuned kernel for that step, clear = generic kernel.

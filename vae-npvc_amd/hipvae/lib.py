@@ -117,6 +117,9 @@ SIGNATURES = {
     'vaenpvc_speaker_stats_workspace_bytes': (_I64, [_I64, _I32, _I32]),
     'vaenpvc_speaker_stats': (C.c_int, [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I64, _I32, _P, _P, _P, _P, C.c_size_t,
                                         _P]),
+    'vaenpvc_resample_plan': (C.c_int, [_I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    'vaenpvc_resample_filter': (C.c_int, [_I32, _I32, _P]),
+    'vaenpvc_resample': (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P]),
     'vaenpvc_unpack_records': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_gather_unpack_records': (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_set_precision': (C.c_int, [_P, C.c_int]),
