@@ -106,6 +106,19 @@ int vaenpvc_set_impl(vaenpvc_ctx* ctx, int impl);
  * precision training mode. */
 int vaenpvc_set_precision(vaenpvc_ctx* ctx, int planes);
 int vaenpvc_get_precision(const vaenpvc_ctx* ctx);
+/* Weight gradients of the merge layer and decoder layer 0 on the VCC2016 geometry (no reference counterpart; same
+ * result, another order of summation).  Nothing non-linear sits between the two layers, so both gradients follow from
+ * dWc = z^T du0 (du0 = gradient at decoder layer 0's pre-LayerNorm output) and the per-speaker sums of du0, pushed
+ * through the conv kernels as 138 pseudo-frames.  mode: 0 = never (one frame-sized GEMM per layer), 1 = from 1 024
+ * frames per call on (default; environment VAENPVC_D0W_FACTOR at context creation), 2 = whenever the kernels serve the
+ * shape.  May be changed between a train step and vaenpvc_train_bwd_target: the backward pass re-makes operands the
+ * forward pass did not leave.  vaenpvc_get_d0w_route: the route the last layered backward pass of this context took. */
+#define VAENPVC_D0W_ROUTE_FP32 0       /* exact-fp32 conv weight-gradient kernel (or the generic kernels / no layered backward pass yet) */
+#define VAENPVC_D0W_ROUTE_FACTOR 1     /* the factorised route */
+#define VAENPVC_D0W_ROUTE_PLANES 2     /* frame-sized plane GEMMs, operand planes of h left by the forward pass */
+#define VAENPVC_D0W_ROUTE_PLANES_REDO 3 /* frame-sized plane GEMMs, operand planes of h re-made by the backward pass */
+int vaenpvc_set_d0w_factor(vaenpvc_ctx* ctx, int mode);
+int vaenpvc_get_d0w_route(const vaenpvc_ctx* ctx);
 
 /* Trainable-tensor table = tf.trainable_variables() of the reference in creation
  * order (model/vae.py:20-24,72-103; util/layers.py:33-64): 44 tensors for the

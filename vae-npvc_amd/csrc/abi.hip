@@ -139,6 +139,14 @@ int vaenpvc_set_precision(vaenpvc_ctx* ctx, int planes) {
 }
 int vaenpvc_get_precision(const vaenpvc_ctx* ctx) { return ctx ? ctx->rt.planes : VAENPVC_E_ARG; }
 
+int vaenpvc_set_d0w_factor(vaenpvc_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return fail(VAENPVC_E_ARG, "d0w factor mode must be 0, 1 or 2");
+  Call call(ctx, false);
+  ctx->rt.d0w_factor = mode;
+  return 0;
+}
+int vaenpvc_get_d0w_route(const vaenpvc_ctx* ctx) { return ctx ? ctx->rt.d0w_route : VAENPVC_E_ARG; }
+
 int vaenpvc_set_bucket_callback(vaenpvc_ctx* ctx, vaenpvc_bucket_cb cb, void* user) {
   if (!ctx) return fail(VAENPVC_E_ARG, "null context");
   Call call(ctx, false);

@@ -857,6 +857,18 @@ __global__ void __launch_bounds__(256) k_segsum_atomic(const float* __restrict__
   }
 }
 
+// rows of a channel-last tensor with halo rows ([rows][HP][CP], position p in row HLO + p) -> canonical frames [rows][C][H]: the
+// factorised weight gradients of decoder layer 0 / the merge layer hand their GEMM results to the conv kernels as pseudo-frames.
+// One thread per element in source order (coalesced reads, 128-byte runs); the halo rows hold sums of zeros and are dropped.
+__global__ void __launch_bounds__(256) k_cl_rows_to_frames(const float* __restrict__ src, float* __restrict__ dst, int rows, int C, int H,
+                                                           int CP, int HLO, int HP) {
+  const int n = rows * H * C;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int c = i % C, t = i / C, p = t % H, r = t / H;
+    dst[((int64_t)r * C + c) * H + p] = src[((int64_t)r * HP + HLO + p) * CP + c];
+  }
+}
+
 // everything the merge backward derives from S (plain stores: nothing else writes these gradients):
 //   blocks [0, nb_w)        : dWy[m][n] = sum_k E[k][m] S[k][n]        (one thread per element)
 //   blocks [nb_w, +nb_e)    : dE[k][m]  = sum_n S[k][n] Wy[m][n]       (one wave per element)

@@ -195,7 +195,12 @@ struct Pk {
   static constexpr int cvwr_e2g = cvwr_d0f + fcr_wfloats(CV_D0F);
   static constexpr int enc0part_ = cvwr_e2g + fcr_wfloats(CV_E2G);
   static constexpr int enc0part = enc0part_;                  // [512][7*16] partial weight gradients of encoder layer 0
-  static constexpr int total = enc0part + 512 * 7 * 16;
+  // factorised weight gradients of decoder layer 0 and the merge layer (d0w_factor_bwd): dWc = z^T du0 [128][63 * 32] and the per-speaker
+  // sums of du0 [ny][63 * 32], both channel-last with halo rows as the planes of du0; the same 138 rows as canonical frames [138][32][57]
+  static constexpr int d0w_c = enc0part + 512 * 7 * 16;
+  static constexpr int d0w_s = d0w_c + 128 * 2016;
+  static constexpr int d0w_y = d0w_s + MERGE_NY * 2016;
+  static constexpr int total = d0w_y + (128 + MERGE_NY) * 1824;
 };
 static_assert(Pk::total <= 8 * 939162 + 65536, "packed weights must fit the scratch region");
 // Kernel selection is a function of the context's two masks (include/vaenpvc_debug.h: vaenpvc_sel_bit), its precision, the
@@ -281,6 +286,17 @@ static inline bool cw_bwd(int site, int64_t F) { return cg_bwd(F) && cv_sel(rt()
 // decoder layer 0's fused forward kernel also writes the channel-last planes of its input h (operand of the layer's view weight gradient)
 static inline bool d0f_leaves_planes(int64_t F) {
   return F >= 1024 && fwd_on(VAENPVC_SEL_DEC0) && fcr_fwd(CV_D0F, F) && bwd_on(VAENPVC_SEL_DEC0) && cw_bwd(CW_D0, F);
+}
+// Weight gradients of decoder layer 0 AND the merge layer from one plane GEMM (backward(): d0w_factor_bwd; Runtime::d0w_factor).  h_f =
+// z_f Wz + T[y_f] goes straight into layer 0's transposed conv, so both gradients are bilinear in (h_f, du0_f) and the per-frame scalars
+// z_f[k] / one-hot(y_f) slide through the frame sum: dWc = z^T du0 and the per-speaker sums of du0 are all that is frame-sized.  Served
+// where both sites are on the plane kernels (layer 0's view weight gradient, the merge step on the plane GEMMs in both passes).
+// Decided by the forward pass too: on this route nothing reads the channel-last planes of h, and decoder layer 0 does not write them.
+constexpr int64_t D0W_FACTOR_MIN_FRAMES = 1024;
+static inline bool d0w_factor_on(int64_t F) {
+  const int mode = rt().d0w_factor;
+  if (mode <= 0 || (mode == 1 && F < D0W_FACTOR_MIN_FRAMES)) return false;
+  return bwd_on(VAENPVC_SEL_DEC0) && cw_bwd(CW_D0, F) && bwd_on(VAENPVC_SEL_MERGE) && pg_step(VAENPVC_SEL_MERGE, F);
 }
 static inline unsigned short* us(float* p) { return reinterpret_cast<unsigned short*>(p); }
 static NtArgs nt_args(const float* Ap, int M, int Kp, const float* Bp, int Np, int N, float* C, int ldc) {
@@ -679,6 +695,7 @@ void decoder_fwd(const Model& m, const float* P, const float* z, const int64_t* 
   if (!weights_packed) prep(m, P, w, F, s);
   const bool z_planes_done = rt().plz_F == F && z == w.z;   // (this step's sampler kernel wrote them: reparam_fwd_planes)
   rt().plz_F = -1;
+  rt().clh_F = -1;
   if (fwd_on(VAENPVC_SEL_MERGE) && pg_fwd(F)) {
     for_planes([&](auto npl) {
       constexpr int NPL = decltype(npl)::value;
@@ -733,9 +750,11 @@ void decoder_fwd(const Model& m, const float* P, const float* z, const int64_t* 
     for_planes([&](auto npl) {
       FcArgs fa{w.h, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const unsigned short*>(w.scratch + Pk::cvwr_d0f),
                 P + m.dec[0].b_off, w.dec_a[0], F};
-      if (w.d_h && d0f_leaves_planes(F)) {   // train mode: the planes of h the weight-gradient GEMM of this layer reads leave the staging
+      // train mode: the planes of h the weight-gradient GEMM of this layer reads leave the staging (the factorised route has no reader for them)
+      if (w.d_h && d0f_leaves_planes(F) && !d0w_factor_on(F)) {
         fa.cl_out = us(w.cl[CL_H]);
         fa.cl_plane = cl_plane(CL_H, F);
+        rt().clh_F = F;
       }
       VAENPVC_TIMED("dec0_fwd", s, fconv_r<decltype(npl)::value>(CV_D0F, fa, s));
     });
@@ -936,6 +955,7 @@ void backward(const Model& m, const float* P, const float* x, const int64_t* y, 
   const int F = (int)F64;
   const bool abf = act_bf16(F64);   // bf16 storage of dec_a[1], dec_a[2] and of the gradients at their activated outputs
   (void)hipMemsetAsync(G, 0, (size_t)m.n_params * 4, s);
+  rt().d0w_route = VAENPVC_D0W_ROUTE_FP32;
   // (SEL_WGRAD_STREAM of the backward mask cleared = no fork for this call: serialised kernels, used by bench.py to
   //  time single kernels without concurrent neighbours)
   // (with two operand planes the fork LOSES from SIDE_STREAM_MAX_FRAMES frames on: the weight-gradient GEMMs hold a whole CU's LDS for
@@ -1248,15 +1268,71 @@ void backward(const Model& m, const float* P, const float* x, const int64_t* y, 
   // d(h) straight to the planes of the two merge GEMMs (the input-gradient kernel owns whole frames and has them in LDS): every consumer
   // of d(h) on this path must be a plane kernel, and the per-speaker sums are then taken from the planes
   const bool dh_planes = rt().d0g_planes && gd0_only_planes && fcr_otl(CV_D0G, rt().planes) && pg_step(VAENPVC_SEL_MERGE, F) && F >= 64;
+  // ---- the factorised weight gradients of decoder layer 0 and the merge layer (d0w_factor_on).  With du0 = d(pre-LN output of layer 0), D =
+  //      layer 0's transposed conv without bias and D^T its input-gradient map:
+  //        dWc[k] = sum_f z_f[k] du0_f  (k < 128),   S[s] = sum_{f: y_f = s} du0_f  (s < 10)            -- the only frame-sized work
+  //        dW_conv = sum_k wgrad_conv(Wz[k], dWc[k]) + sum_s wgrad_conv(T[s], S[s]),   dWz[k] = D^T(dWc[k]),   Sg[s] = D^T(S[s])
+  //      i.e. the conv weight-gradient and input-gradient kernels on 138 pseudo-frames (inputs [Wz rows; T rows], gradients [dWc; S]); Sg are
+  //      the per-speaker sums of d(h) that k_merge_small consumes.  Both frame-sized operands are channel-last rows of 63 x 32 (planes of du0).
+  const bool d0w = d0w_factor_on(F);
+  static_assert(CLD[CL_GD0].HP * CLD[CL_GD0].CP == 2016 && CLD[CL_GD0].C * CLD[CL_GD0].H == 1824 && GD0s::KC * GD0s::HIN == 1824 && GD0s::N * GD0s::HOUT == 1539,
+                "pseudo-frames of the factorised route");
+  constexpr int D0W_ROW = 2016, D0W_FR = 1824;
+  float* const d0w_ys = w.scratch + Pk::d0w_y + 128 * D0W_FR;   // the speaker rows of the pseudo-batch's gradients
+  auto d0w_unpack = [&](const float* src, float* dst, int rows, const char* tag, hipStream_t st) {
+    const ClDesc& d = CLD[CL_GD0];
+    VAENPVC_TIMED(tag, st, hipLaunchKernelGGL(k_cl_rows_to_frames, dim3((unsigned)cdiv(rows * D0W_FR, 256)), dim3(256), 0, st, src, dst, rows,
+                                                       d.C, d.H, d.CP, d.HLO, d.HP));
+  };
+  // the chain's stream: S from the planes of du0, Sg = D^T(S) (what the merge block behind us needs on this stream)
+  auto d0w_sums = [&]() {
+    float* Sc = w.scratch + Pk::d0w_s;
+    for_planes([&](auto npl) {
+      constexpr int NPL = decltype(npl)::value;
+      // (the chunk partials go to dy_tmp: the LayerNorm backward passes, its last readers, are behind us on this stream; one chunk = the sums themselves)
+      const bool one = F < 64;
+      int nch = 0;
+      VAENPVC_TIMED("merge_segsum", s, (nch = launch_segsum_planes<NPL, MERGE_NY>(us(w.cl[CL_GD0]), cl_plane(CL_GD0, F), y, D0W_ROW, D0W_ROW, F,
+                                                                                  one ? Sc : w.dy_tmp, s)));
+      if (!one) VAENPVC_TIMED("merge_segsum", s, launch_sum_parts(w.dy_tmp, nch, MERGE_NY * D0W_ROW, Sc, s));
+    });
+    d0w_unpack(Sc, d0w_ys, MERGE_NY, "merge_segsum", s);
+    VAENPVC_TIMED("merge_wgrad", s, launch_convgemm<GD0s>(conv_args(d0w_ys, nullptr, nullptr, nullptr, w.scratch + Pk::gd0, nullptr,
+                                                                    w.scratch + Pk::merge_s, MERGE_NY), nsplit_for<GD0s>(MERGE_NY), s));
+  };
+  // the weight-gradient stream: dWc by one plane GEMM over the frames, then the three conv launches on the pseudo-frames
+  auto d0w_wgrads = [&]() {
+    float* Wc = w.scratch + Pk::d0w_c;
+    float* Yc = w.scratch + Pk::d0w_y;
+    (void)hipMemsetAsync(Wc, 0, (size_t)128 * D0W_ROW * 4, s2);
+    for_planes([&](auto npl) {
+      constexpr int NPL = decltype(npl)::value;
+      TnpArgs t = tnp_args(w.pl_z, 128, w.cl[CL_GD0], D0W_ROW, 128, D0W_ROW, F, Wc, D0W_ROW);
+      t.b_plane = cl_plane(CL_GD0, F);   // (channel-last planes carry a zero tail behind every plane)
+      VAENPVC_TIMED("dec0_wgrad", s2, (launch_gemm_tn<NPL, TN_EPI_PLAIN>(t, TN_WGS_DENSE, s2)));
+    });
+    d0w_unpack(Wc, Yc, 128, "dec0_wgrad", s2);
+    const ConvL& l = m.dec[0];
+    WgArgs az{Yc, nullptr, nullptr, nullptr, P + m.wz_off, nullptr, nullptr, nullptr, G + l.w_off, 128, 0};
+    WgArgs ay{d0w_ys, nullptr, nullptr, nullptr, w.scratch + Pk::merge_tb, nullptr, nullptr, nullptr, G + l.w_off, MERGE_NY, 0};
+    VAENPVC_TIMED("dec0_wgrad", s2, launch_convwgrad<WD0>(az, WGS, s2); launch_convwgrad<WD0>(ay, WGS, s2));
+    VAENPVC_TIMED("merge_wgrad", s2, launch_convgemm<GD0s>(conv_args(Yc, nullptr, nullptr, nullptr, w.scratch + Pk::gd0, nullptr, G + m.wz_off, 128),
+                                                           nsplit_for<GD0s>(128), s2));
+  };
   // ---- d0
   if (bwd_on(VAENPVC_SEL_DEC0)) {
     const ConvL& l = m.dec[0];
     WgArgs a{w.d_dec_a[0], nullptr, nullptr, nullptr, w.h, nullptr, nullptr, nullptr, G + l.w_off, F, 0};
     const bool rg = fcr_bwd(CV_D0G, F), vg = !rg && cv_bwd(CV_D0G, F), vw = cw_bwd(CW_D0, F);
     if ((vg || vw) && !gd0_planes) gsplit(CL_GD0, w.d_dec_a[0], "dec0_gsplit");
-    if (vw && !fwd_planes(VAENPVC_SEL_DEC0, CV_D0F, F) && !d0f_leaves_planes(F)) asplit(CL_H, w.h, nullptr, nullptr, "dec0_asplit");
+    // (the planes of h: from the forward pass of THIS step, or re-made here -- a forward pass that ran under the factorised route left none)
+    const bool h_planes = fwd_planes(VAENPVC_SEL_DEC0, CV_D0F, F) || (d0f_leaves_planes(F) && rt().clh_F == F);
+    if (vw && !d0w && !h_planes) asplit(CL_H, w.h, nullptr, nullptr, "dec0_asplit");
+    rt().d0w_route = d0w ? VAENPVC_D0W_ROUTE_FACTOR : !vw ? VAENPVC_D0W_ROUTE_FP32 : h_planes ? VAENPVC_D0W_ROUTE_PLANES : VAENPVC_D0W_ROUTE_PLANES_REDO;
+    if (d0w) d0w_sums();
     ready();
-    if (vw) vwgrad(CW_D0, G + l.w_off, "dec0_wgrad");
+    if (d0w) d0w_wgrads();
+    else if (vw) vwgrad(CW_D0, G + l.w_off, "dec0_wgrad");
     else VAENPVC_TIMED("dec0_wgrad", s2, launch_convwgrad<WD0>(a, WGS, s2));
     if (!dec_bias_done[0]) generic::bias_grad(w.d_dec_a[0], G + l.b_off, F, l.cout, l.hout, s);
     if (rg) rdgrad(CV_D0G, w.scratch + Pk::cvw + cv_woff(CV_D0G), w.d_dec_a[0], w.d_h, "dec0_dgrad", gd0_only_planes ? w.cl[CL_GD0] : nullptr,
@@ -1277,6 +1353,10 @@ void backward(const Model& m, const float* P, const float* x, const int64_t* y, 
     if (pgm) {
       for_planes([&](auto npl) {
         constexpr int NPL = decltype(npl)::value;
+        if (d0w) {   // (weight gradient and per-speaker sums are done: only the planes of d(h) for the input-gradient GEMM, where nothing made them yet)
+          if (!dh_planes) VAENPVC_TIMED("merge_dsplit", s, launch_split<NPL>(split_args(w.d_h, 1539, 1600, F, us(w.pl_dh)), s));
+          return;
+        }
         if (F >= 64) {   // the planes of d(h) and the per-speaker column sums S in one pass over d(h)
         // (the chunk partials go to dy_tmp: the decoder's backward pass, its only user on this path, is behind us on this stream)
         int nch = 0;
@@ -1300,7 +1380,7 @@ void backward(const Model& m, const float* P, const float* x, const int64_t* y, 
     }
     // S[k] = per-speaker column sums of d(h); the bias gradients, dWy = E^T S and dE = S Wy^T follow from it
     float* Sg = w.scratch + Pk::merge_s;
-    if (!(pgm && F >= 64)) {
+    if (!(pgm && F >= 64) && !d0w) {
       (void)hipMemsetAsync(Sg, 0, (size_t)MERGE_NY * 1539 * 4, s);
       int ch = cmax(1, cmin_(cdiv(F, 64), 128)), fc = cdiv(F, ch);
       VAENPVC_TIMED("merge_segsum", s, hipLaunchKernelGGL(k_segsum_atomic<MERGE_NY>, dim3((unsigned)cdiv(1539, 256), (unsigned)cdiv(F, fc)), dim3(256), 0, s,

@@ -55,6 +55,9 @@ struct Runtime {
   bool toep_f32 = false;        // VAENPVC_TOEP=f32: exact-fp32 MFMA kernels for the 1025-tap layer
   bool side_enabled = true;     // VAENPVC_SIDE_STREAM=0 disables the internal weight-gradient stream
   bool side_forced = false;     // VAENPVC_SIDE_STREAM=1: the second stream at every batch size
+  int d0w_factor = 1;           // VAENPVC_D0W_FACTOR: decoder layer 0's and the merge layer's weight gradients from ONE plane GEMM over (z, d(pre-LN output of
+                                // layer 0)) and conv kernels on 138 pseudo-frames (gfx950_layers.hip: d0w_factor_on): 1 = from 1 024 frames on, 2 = whenever
+                                // the shape is served (parity tests), 0 = never: the frame-sized weight-gradient GEMM of each layer
   int frame_max = 512;          // VAENPVC_FRAME_MAX: largest batch on the whole-frame-per-workgroup kernels (gfx950_frame.h); 0 = never.
                                 // VAENPVC_SEL_FRAME of a mask cleared = the layered kernels for that pass of this context (A/B, parity tests)
   // ---- what the last train forward of this context left in the workspace (vaenpvc_train_bwd_target re-uses it): batch size, kernel
@@ -65,6 +68,8 @@ struct Runtime {
   const void* last_ws = nullptr;
   int64_t plz_F = -1;           // batch size whose z planes tuned::reparam_fwd_planes left for the decoder_fwd that follows (-1: none)
   int64_t dxh_post_F = -1;      // batch size whose d(xh) planes / column 512 / bias parts tuned::loss_fwd_post left for the backward pass (-1: none)
+  int64_t clh_F = -1;           // batch size whose channel-last planes of h decoder layer 0's fused forward kernel left for the layer's view weight gradient (-1: none)
+  int d0w_route = 0;            // weight-gradient route of decoder layer 0 in the last layered backward call (vaenpvc_get_d0w_route: VAENPVC_D0W_ROUTE_*)
   // ---- device binding: created lazily on the device that is current at the first launch
   int device = -1;
   hipStream_t s2 = nullptr;

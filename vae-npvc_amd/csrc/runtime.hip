@@ -37,6 +37,7 @@ void Runtime::read_env() {
   if (const char* e = getenv("VAENPVC_CG_SF_RING")) cg_sf_ring = atoi(e);
   if (const char* e = getenv("VAENPVC_CG_PF_RING")) cg_pf_ring = atoi(e);
   if (const char* e = getenv("VAENPVC_NT_AR")) nt_ar = atoi(e);
+  if (const char* e = getenv("VAENPVC_D0W_FACTOR")) d0w_factor = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
   if (const char* e = getenv("VAENPVC_FRAME_MAX")) frame_max = atoi(e) < 0 ? 0 : (atoi(e) > 1024 ? 1024 : atoi(e));
   if (const char* e = getenv("VAENPVC_FB_LAYERS")) fb_layers_env = (long)strtoul(e, nullptr, 0);
   if (const char* e = getenv("VAENPVC_ACT_BF16")) act_bf16 = atoi(e) != 0;

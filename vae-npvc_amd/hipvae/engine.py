@@ -118,6 +118,15 @@ class Engine(object):
     def precision(self):
         return int(self.lib.vaenpvc_get_precision(self.ctx))
 
+    def set_d0w_factor(self, mode):
+        """0 / 1 / 2: decoder layer 0's and the merge layer's weight gradients from one plane GEMM (include/vaenpvc.h)."""
+        L.check(self.lib.vaenpvc_set_d0w_factor(self.ctx, int(mode)), 'set_d0w_factor')
+
+    @property
+    def d0w_route(self):
+        """VAENPVC_D0W_ROUTE_* of the last layered backward pass: 0 fp32 kernel, 1 factorised, 2 plane GEMMs, 3 plane GEMMs after re-making the planes of h."""
+        return int(self.lib.vaenpvc_get_d0w_route(self.ctx))
+
     def set_tuned_masks(self, fwd=0xffffffff, bwd=0xffffffff):
         """Per-step tuned/generic kernel selection of THIS engine's context (developer hook, include/vaenpvc_debug.h)."""
         L.check(self.lib.vaenpvc_set_tuned_masks(self.ctx, fwd & 0xffffffff, bwd & 0xffffffff), 'set_tuned_masks')

@@ -124,6 +124,8 @@ SIGNATURES = {
     'vaenpvc_gather_unpack_records': (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     'vaenpvc_set_precision': (C.c_int, [_P, C.c_int]),
     'vaenpvc_get_precision': (C.c_int, [_P]),
+    'vaenpvc_set_d0w_factor': (C.c_int, [_P, C.c_int]),
+    'vaenpvc_get_d0w_route': (C.c_int, [_P]),
     'vaenpvc_train_fwd_bwd_seeded': (C.c_int, [_P, _P, _P, _P, _U64, _U64, _P, _I64, _P, _P, _P, C.c_size_t, _P]),
     'vaenpvc_loss_fwd_seeded': (C.c_int, [_P, _P, _P, _P, _U64, _U64, _I64, _P, _P, C.c_size_t, _P]),
     'vaenpvc_philox_normal': (C.c_int, [_U64, _U64, _P, _I64, _P]),
